@@ -11,7 +11,16 @@ may then be omitted, and must equal WORLD_SIZE when given).  Rank 0 embeds the g
 only exchange step); each rank then processes its own probes independently
 (weak scaling: N x batch faces per step).
 
-Also reported:
+A plain run sets up, warms up, times ``--steps`` steps and prints the line (throughput,
+``ms_per_step``, the workload's description, ``top1_self_match`` of the last step's outputs).
+``--dump-outputs DIR`` also writes what the last timed step computed (embeddings, top-k indices
+and scores of this rank's batch) as ``DIR/<name>.npy``; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.  With N > 1 the line also holds
+  gallery_exchange  the broadcast's bytes, ms (first, and median of
+                --exchange-reps repeats) and GB/s, max over ranks; plus the fastest and
+                slowest rank's ms/step (rank_ms_per_step_min/max)
+
+With ``--full`` the line also reports:
   roofline      the dominant conv kernel family (wino4_kernel for the stride-1 3x3 convs
                 under the f32 default): algorithmic (direct-conv) FLOP / summed
                 HIP-event time of its launches, vs the 157.3 TF dense fp32 MFMA
@@ -19,9 +28,6 @@ Also reported:
                 The events are recorded in a second timed pass of the same K steps
                 (ms_per_step_profiled_pass): an event pair around every launch adds
                 ~0.8 ms per IR-101 step, so the throughput pass runs without them.
-  gallery_exchange (N > 1)  the broadcast's bytes, ms (first, and median of
-                --exchange-reps repeats) and GB/s, max over ranks; plus the fastest and
-                slowest rank's ms/step (rank_ms_per_step_min/max)
   cpu_baseline  the oracle (PyTorch-CPU IR-101 + reference-style per-probe
                 search) on rank 0's host cores, on a bounded sample.
 """
@@ -58,8 +64,13 @@ def parse():
     ap.add_argument("--same-gpu", action="store_true",
                     help="testing: every rank on cuda:0 (needs --dist-backend gloo; RCCL refuses two ranks "
                          "on one GPU)")
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled pass (roofline; C4: the detector's too) and "
+                         "the CPU baseline; without it the run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (embeddings, topk_index, topk_score) as DIR/<name>.npy")
     ap.add_argument("--config", choices=["c2", "c3", "c4", "c5"], default="c3",
                     help="BASELINE.json config: c2 IR-50 embed-only B=256; c3 IR-101 embed+match B=256 G=1k "
                          "(default, the headline metric); c4 1080p frames -> SCRFD-10G detect -> align + "
@@ -80,12 +91,12 @@ def parse():
                     help="stride-1 3x3 convs: Winograd F(4x4,3x3), F(2x2,3x3) or the direct implicit GEMM (all f32)")
     ap.add_argument("--lanes-min", type=int, default=None,
                     help="a forward of n >= 2x this many crops runs as two concurrent halves (0: one lane; default: library's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: budget of the CPU baseline sample")
     ap.add_argument("--exchange-reps", type=int, default=3,
                     help="N > 1: timed repeats of the gallery broadcast after the real one (steady-state rate)")
     ap.add_argument("--traffic-json", default=None,
-                    help="PMC-derived HBM bytes per conv launch (tools/prof_summary.py --json); "
+                    help="--full: PMC-derived HBM bytes per conv launch (tools/prof_summary.py --json); "
                          "default: the newest profiles/r*/layers_pmc.json")
     return ap.parse_args()
 
@@ -304,6 +315,31 @@ def detector_roofline(detector, frames, det_stream, build, reps=5):
                     "reference network's direct-conv count (unpadded channels, full 640x640 canvas), "
                     "detect_alg_tflops its rate over the whole detect (letterbox to NMS + D2H)")}
     return out
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 4096  # 64 MB in all, the .npy headers included
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(dirname, arrays, suffix="", limit=DUMP_LIMIT_BYTES):
+    """Write per-face output arrays (name -> [n, ...] numpy array, one row per face of the step) as
+    ``dirname/<name><suffix>.npy``: floating arrays as float32, integer ones as float64 (exact).  When
+    the rows together exceed ``limit`` bytes, a fixed seeded sample of the rows is written instead,
+    with the sampled row numbers as ``rows<suffix>.npy``.  Returns the row numbers written."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype.kind == "f" else np.float64)
+           for k, v in arrays.items()}
+    n = next(iter(out.values())).shape[0]
+    rows = np.arange(n)
+    per_row = sum(v.nbytes // max(n, 1) for v in out.values())
+    if n * per_row > limit:
+        keep = max(1, int(limit // (per_row + 8)))  # + the row number itself
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), v)
+    return rows
 
 
 PRESETS = {"c2": ("ir_50", 0), "c3": ("ir_101", 1000), "c4": ("ir_101", 1000), "c5": ("ir_101", 100_000)}
@@ -627,17 +663,26 @@ def main():
         rank_spread[:] = [tmin.item(), t.item()]
         return t.item()
 
-    # throughput: the K steps with nothing else on the queue; then the same K steps again with a
-    # HIP event pair around every launch (fr_profile_*) for the per-kernel roofline -- the event
-    # records add ~0.8 ms per IR-101 step, so they stay out of the throughput pass
+    # throughput: the K steps with nothing else on the queue; then (--full) the same K steps again
+    # with a HIP event pair around every launch (fr_profile_*) for the per-kernel roofline -- the
+    # event records add ~0.8 ms per IR-101 step, so they stay out of the throughput pass
     rank_spread = [0.0, 0.0]
     tmax = timed_steps()
     rank_ms = [round(x / args.steps * 1e3, 3) for x in rank_spread]
-    emb.model.profile_enable(True)
-    emb.model.profile_read()
-    tprof = timed_steps()
-    prof = emb.model.profile_read()
-    emb.model.profile_enable(False)
+    if args.dump_outputs:
+        # what the last timed step handed back: this rank's embeddings and, with a gallery, its top-k
+        last = {"embeddings": e_out.cpu().numpy()}
+        if G > 0:
+            last["topk_index"] = idx.cpu().numpy()
+            last["topk_score"] = score.cpu().numpy()
+        dump_outputs(args.dump_outputs, last, suffix="" if rank == 0 else f"_rank{rank}")
+    prof = tprof = None
+    if args.full:
+        emb.model.profile_enable(True)
+        emb.model.profile_read()
+        tprof = timed_steps()
+        prof = emb.model.profile_read()
+        emb.model.profile_enable(False)
     if args.config == "c4" and det_pool is not None:
         for f in pending:  # the detection the last step started (no timed step consumes it)
             f.result()
@@ -653,8 +698,8 @@ def main():
         dist.all_reduce(t1, op=dist.ReduceOp.MIN)
         top1_ok = t1.item()
 
-    if rank == 0:
-        faces = world * args.batch * args.steps
+    faces = world * args.batch * args.steps
+    if rank == 0 and args.full:
         # dominant kernel = the conv family with the most time in the timed region (HIP events on the
         # launch stream): the Winograd kernel for the f32 default, the direct implicit-GEMM one otherwise
         fams = {f: prof[f] for f in ("winograd", "direct") if prof[f]["launches"]}
@@ -715,6 +760,7 @@ def main():
                                              "launches": d["launches"],
                                              "share_of_step": round(d["ms"] / max(prof["total_ms"], 1e-9), 4)}
         roofline["conv_family_tflops"] = round(conv_tflops, 3)
+    if rank == 0:
         out = {
             "metric": METRIC if args.config == "c3" and args.model_type == "adaface" else (
                 f"faces/sec detect+align+quality+embed+match from 1080p frames (IR-101, gallery={G})"
@@ -727,7 +773,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(tmax / args.steps * 1e3, 3),
-            "ms_per_step_profiled_pass": round(tprof / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -761,9 +806,11 @@ def main():
             "flop_per_face": flop_per_face(args.arch, G, args.model_type),
             "path_tflops": round(faces / tmax * flop_per_face(args.arch, G, args.model_type) / 1e12, 2),
             "top1_self_match": top1_ok,
-            "roofline": roofline,
         }
-        if args.config == "c4":
+        if args.full:
+            out["ms_per_step_profiled_pass"] = round(tprof / args.steps * 1e3, 3)
+            out["roofline"] = roofline
+        if args.full and args.config == "c4":
             roofline["detector"] = detector_roofline(detector, frames, det_stream, build)
         if world > 1:
             # the fastest and the slowest rank's timed region (value uses the slowest)
@@ -773,7 +820,7 @@ def main():
             if exchange is not None:
                 out["gallery_exchange_ms"] = exchange["ms"]
                 out["gallery_exchange_GBps"] = exchange["GBps_aggregate"]
-        if world == 1 and not args.no_cpu_baseline and args.model_type == "adaface":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model_type == "adaface":
             gnp = gallery.cpu().numpy() if G > 0 else np.zeros((0, 512), np.float32)
             if args.config == "c4":
                 out["cpu_baseline"] = cpu_baseline_c4(sd, detector_sd, gnp, frames.cpu().numpy(), lms,
@@ -781,7 +828,7 @@ def main():
             else:
                 sample = W.probe_crops(gal_crops, 1024, seed=W.CROP_SEED_PROBE)
                 out["cpu_baseline"] = cpu_baseline(args.arch, sd, gnp, sample, args.cpu_seconds)
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if world > 1:

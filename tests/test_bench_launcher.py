@@ -65,6 +65,29 @@ def test_gpu_count_never_initialises_hip(monkeypatch):
         assert b.count_gpus() <= 1
 
 
+def test_dump_outputs_formats_and_seeded_sample(tmp_path):
+    """--dump-outputs: float arrays as float32, integer ones as float64 (exact); past the byte limit
+    the same seeded rows every time, with their numbers beside them."""
+    import numpy as np
+    b = _bench_module()
+    e = np.arange(40 * 8, dtype=np.float32).reshape(40, 8)
+    i = (np.arange(40 * 2, dtype=np.int32).reshape(40, 2) + 2 ** 30)
+    rows = b.dump_outputs(str(tmp_path / "a"), {"embeddings": e, "topk_index": i})
+    assert np.array_equal(rows, np.arange(40)) and sorted(os.listdir(tmp_path / "a")) == ["embeddings.npy", "topk_index.npy"]
+    got = np.load(tmp_path / "a" / "topk_index.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, i)
+    assert np.load(tmp_path / "a" / "embeddings.npy").dtype == np.float32
+    # 40 rows x (32 + 16) bytes = 1,920 > 560: 10 rows of 48 + 8 bytes fit
+    for name in ("b", "c"):
+        rows = b.dump_outputs(str(tmp_path / name), {"embeddings": e, "topk_index": i}, suffix="_rank1", limit=560)
+        assert len(rows) == 10 and len(set(rows)) == 10 and list(rows) == sorted(rows)
+        assert np.array_equal(np.load(tmp_path / name / "rows_rank1.npy"), rows)
+        assert np.array_equal(np.load(tmp_path / name / "embeddings_rank1.npy"), e[rows])
+        assert np.array_equal(np.load(tmp_path / name / "topk_index_rank1.npy"), i[rows])
+        assert sum(os.path.getsize(tmp_path / name / f) - 128 for f in os.listdir(tmp_path / name)) <= 560
+    assert np.array_equal(np.load(tmp_path / "b" / "rows_rank1.npy"), np.load(tmp_path / "c" / "rows_rank1.npy"))
+
+
 def test_pmc_figures_attach_only_to_the_profiled_build(tmp_path):
     """bench.py's roofline.traffic / mfma_busy come from a committed PMC profile only when that
     profile was stamped with the loaded library's build (fr_version() hash)."""

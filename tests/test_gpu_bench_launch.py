@@ -17,9 +17,10 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra, timeout=420):
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           *extra]
+def _run(*extra, timeout=420, full=True):
+    """One bench run; ``full`` asks for the roofline pass too (the CPU baseline stays off)."""
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
+           *(("--full", "--no-cpu-baseline") if full else ()), *extra]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-4000:]
@@ -76,3 +77,26 @@ def test_bench_gpus1_line_unchanged_shape():
     assert "gallery_exchange_ms" not in out and "rank_ms_per_step_min" not in out
     assert out["top1_self_match"] == 1.0
     assert out["roofline"]["bound"] == "mfma"
+
+
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path, golden_dir):
+    """Without --full the line carries the throughput figures only, and --dump-outputs writes what
+    the last timed step computed: C3's probe embeddings and top-5 are the reference's own
+    (tests/golden/c3_ir_101.npz, the bounds of test_gpu_pipeline.test_c3_exact_config_vs_reference)."""
+    import numpy as np
+    d = tmp_path / "out"
+    out = _run("--dump-outputs", str(d), full=False)
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 256 * 2 / (out["ms_per_step"] * 2 / 1e3)) <= 1e-3 * out["value"] + 0.02
+    assert out["unit"] == "faces/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["top1_self_match"] == 1.0
+    for moved in ("roofline", "cpu_baseline", "ms_per_step_profiled_pass"):
+        assert moved not in out
+    assert sorted(os.listdir(d)) == ["embeddings.npy", "topk_index.npy", "topk_score.npy"]
+    e, idx, sc = (np.load(d / f"{n}.npy") for n in ("embeddings", "topk_index", "topk_score"))
+    assert e.dtype == np.float32 and e.shape == (256, 512)
+    assert idx.dtype == np.float64 and idx.shape == (256, 5) and sc.dtype == np.float32 and sc.shape == (256, 5)
+    g = np.load(os.path.join(golden_dir, "c3_ir_101.npz"))
+    assert np.abs(e - g["probe_emb"]).max() <= 1e-5
+    assert np.array_equal(idx[:, 0], g["search_idx"][:, 0])
+    assert np.abs(sc - g["search_score"]).max() <= 1e-4

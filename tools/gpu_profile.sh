@@ -7,7 +7,8 @@ export TMPDIR=/tmp
 TAG=${TAG:-r1}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-BARGS=${BENCH_ARGS:-"--steps 5 --warmup 2 --no-cpu-baseline"}
+# --full: prof_summary.py aligns the full-batch forwards of the one-lane profiled pass
+BARGS=${BENCH_ARGS:-"--full --steps 5 --warmup 2 --no-cpu-baseline"}
 # the library build the profile is of (fr_version(): "... build <content hash>"); bench.py attaches
 # the PMC figures only to runs of the same build
 python3 -c "from facerecognitionpipeline_amd import _lib; print(_lib.load().fr_version().decode())" > $OUT/build.txt
