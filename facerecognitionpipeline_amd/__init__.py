@@ -8,7 +8,8 @@ fallback.
 """
 from .arch import block_specs, flop_per_face, state_dict_schema  # noqa: F401
 
-__all__ = ["FaceEmbedder", "GalleryManager", "FaceMatcher", "block_specs", "flop_per_face", "state_dict_schema"]
+__all__ = ["FaceEmbedder", "GalleryManager", "FaceMatcher", "StudentEnrollment", "block_specs", "flop_per_face",
+           "state_dict_schema"]
 
 
 def __getattr__(name):
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name == "FaceMatcher":
         from .face_matcher import FaceMatcher
         return FaceMatcher
+    if name == "StudentEnrollment":
+        from .enroll_students import StudentEnrollment
+        return StudentEnrollment
     raise AttributeError(name)

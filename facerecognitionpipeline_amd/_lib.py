@@ -35,6 +35,7 @@ _SIGNATURES = {
     "fr_embed": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     "fr_embed_host": (_I, [_P, _P, _I, _I, _I, _P, _I]),
     "fr_resize_crops": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "fr_augment_faces": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "fr_gallery_set": (_I, [_P, _P, _I, _I, _I, _P]),
     "fr_gallery_size": (_I, [_P, ctypes.POINTER(_I)]),
     "fr_gallery_write_rows": (_I, [_P, _I, _I, _P, _I, _P]),
@@ -159,6 +160,27 @@ class Handle:
         """cv2.resize(INTER_LINEAR) of uint8 [n,H,W,3] device crops into out [n,112,112,3]."""
         check(self._lib.fr_resize_crops(self.h, ptr(src), src.shape[0], src.shape[1], src.shape[2], ptr(out),
                                         stream_of(self.device)), self.h)
+
+    def augment_faces(self, crops: torch.Tensor, num_augmentations: int = 8,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The first ``num_augmentations`` (1..14) entries of the reference's
+        ``augment_face_for_enrollment`` list for every uint8 [n,H,W,3] device crop -> uint8
+        [n,A,H,W,3]; ``reshape(n * A, H, W, 3)`` is the reference's ``all_face_images`` order."""
+        if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3:
+            raise ValueError("expected uint8 [n,H,W,3] RGB crops")
+        if crops.device != self.device:
+            raise ValueError(f"crops are on {crops.device}, the handle on {self.device} (no CPU fallback)")
+        crops = crops.contiguous()
+        n, H, W = crops.shape[0], crops.shape[1], crops.shape[2]
+        A = int(num_augmentations)
+        shape = (n, max(A, 0), H, W, 3)
+        if out is None:
+            out = torch.empty(shape if 1 <= A <= 14 else (0,), dtype=torch.uint8, device=self.device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 {list(shape)} tensor on {self.device}")
+        check(self._lib.fr_augment_faces(self.h, ptr(crops), n, H, W, A, ptr(out), stream_of(self.device)), self.h)
+        return out
 
     # -- gallery -----------------------------------------------------------
     def gallery_set(self, E: torch.Tensor, tag=None) -> None:

@@ -11,6 +11,7 @@
 // is summed in numpy's order (ndarray.var, below), so it is bitwise the
 // reference's.  HBM-bound gathers (a 112x112x3 crop reads ~4x its size at most).
 #include "frhip_kernels.h"
+#include "warp_map.h"
 
 // The map arithmetic must round exactly like OpenCV (separate double mul and add).
 #pragma clang fp contract(off)
@@ -28,15 +29,8 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const uint8_t* __restr
   if (pix >= S * S) return;
   const int oy = pix / S, ox = pix - oy * S;
   const double* m = minv ? minv + face * 6 : maps.m[face];
-  const long long X0 = (long long)__builtin_rint((m[1] * oy + m[2]) * 1024.0) + 16;
-  const long long Y0 = (long long)__builtin_rint((m[4] * oy + m[5]) * 1024.0) + 16;
-  const long long adx = (long long)__builtin_rint(m[0] * ox * 1024.0);
-  const long long bdx = (long long)__builtin_rint(m[3] * ox * 1024.0);
-  const long long X = (X0 + adx) >> 5, Y = (Y0 + bdx) >> 5;
-  const int sx = (int)(X >> 5), sy = (int)(Y >> 5);
-  const int fx = (int)(X & 31), fy = (int)(Y & 31);
-  const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32;
-  const int w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
+  const WarpTap t = warp_tap(m, warp_row(m, oy), ox);
+  const int sx = t.sx, sy = t.sy;
   const bool in_x0 = (unsigned)sx < (unsigned)W, in_x1 = (unsigned)(sx + 1) < (unsigned)W;
   const bool in_y0 = (unsigned)sy < (unsigned)H, in_y1 = (unsigned)(sy + 1) < (unsigned)H;
   uint8_t* o = out + ((long long)face * S * S + pix) * 3;
@@ -46,8 +40,7 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const uint8_t* __restr
     const int p01 = (in_y0 && in_x1) ? frame[((long long)sy * W + sx + 1) * 3 + c] : 0;
     const int p10 = (in_y1 && in_x0) ? frame[((long long)(sy + 1) * W + sx) * 3 + c] : 0;
     const int p11 = (in_y1 && in_x1) ? frame[((long long)(sy + 1) * W + sx + 1) * 3 + c] : 0;
-    int v = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + (1 << 14)) >> 15;
-    o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    o[c] = warp_blend(t, p00, p01, p10, p11);
   }
 }
 

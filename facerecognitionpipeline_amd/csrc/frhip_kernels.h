@@ -238,6 +238,18 @@ size_t blur_lds_bytes(int H, int W);
 size_t blur_workspace_bytes(int n, int H, int W);
 hipError_t launch_blur(const uint8_t* crops, int n, int H, int W, int C, double* var, void* ws, hipStream_t s);
 
+// Enrollment augmentation (augment.hip): A <= AUG_VARIANTS variants of each of n uint8 crops
+// [n][H][W][3] -> out [n][A][H][W][3] (1 <= H, W <= 8192; out must not overlap crops).  The
+// host-built tables travel by value in the kernel arguments (1.2 KB), so the launch needs no copy
+// and nothing for the caller to wait on.
+constexpr int AUG_VARIANTS = 14;
+struct AugTables {
+  double minv[4][6];    // inverse maps of the rotations by -10, -5, 5, 10 degrees (variants 2..5)
+  uint8_t lut[4][256];  // contrast 0.85, 0.92, 1.08, 1.15 of every byte value (variants 10..13)
+};
+hipError_t launch_augment(const uint8_t* crops, int n, int H, int W, int A, const AugTables& tab, uint8_t* out,
+                          hipStream_t s);
+
 // Gallery templates (GalleryManager._aggregate_embeddings) for n_students CSR slices of
 // emb [total][512]; offsets: device [n_students + 1]; out: [n_students][512]; kept: [n] or NULL.
 constexpr int TEMPLATE_MAX_SAMPLES = 1024;

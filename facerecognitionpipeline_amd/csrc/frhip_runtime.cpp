@@ -1278,6 +1278,30 @@ void invert_affine(const double Mf[6], double Mi[6]) {
   m[5] = b2;
   memcpy(Mi, m, sizeof(m));
 }
+
+// Host tables of fr_augment_faces for crops of H x W (enroll_students.py:26-39).  Rotations:
+// cv2.getRotationMatrix2D((W / 2, H / 2), angle, 1.0) in double, as OpenCV builds it, inverted as
+// warpAffine inverts it.  Contrast: numpy multiplies a float32 array by a Python float in float32,
+// clips in float32 and truncates.
+void augment_tables(int H, int W, AugTables* t) {
+  const double angles[4] = {-10, -5, 5, 10};
+  const double cx = W / 2, cy = H / 2;
+  for (int i = 0; i < 4; ++i) {
+    const double rad = angles[i] * (M_PI / 180);
+    const double a = std::cos(rad), b = std::sin(rad);
+    const double Mf[6] = {a, b, (1 - a) * cx - b * cy, -b, a, b * cx + (1 - a) * cy};
+    invert_affine(Mf, t->minv[i]);
+  }
+  const double alphas[4] = {0.85, 0.92, 1.08, 1.15};
+  for (int i = 0; i < 4; ++i) {
+    const float alpha = (float)alphas[i];
+    for (int p = 0; p < 256; ++p) {
+      float r = (float)p * alpha;
+      r = r < 0.f ? 0.f : (r > 255.f ? 255.f : r);
+      t->lut[i][p] = (uint8_t)r;
+    }
+  }
+}
 #pragma clang fp contract(on)
 
 void reference_template(int S, float t[10]) {
@@ -1676,6 +1700,30 @@ int fr_resize_crops(fr_handle* h, const uint8_t* src, int n, int height, int wid
   if (n == 0) return FR_OK;
   DeviceGuard dg(h->device);
   return resize_device(h, src, n, height, width, dst, (hipStream_t)stream);
+}
+
+int fr_augment_faces(fr_handle* h, const uint8_t* crops, int n, int height, int width, int num_augmentations,
+                     uint8_t* out, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = check_crop_size(h, height, width)) return rc;
+  if (num_augmentations > FR_AUGMENT_MAX && num_augmentations <= 16)
+    return fail(h, FR_ERR_UNSUPPORTED,
+                "num_augmentations 15 and 16 (cv2.GaussianBlur and the unseeded np.random.normal noise) are not "
+                "implemented; at most " + std::to_string(FR_AUGMENT_MAX));
+  if (num_augmentations < 1 || num_augmentations > FR_AUGMENT_MAX)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "num_augmentations must be in [1, " + std::to_string(FR_AUGMENT_MAX) + "]");
+  if (n < 0 || (n > 0 && (!crops || !out))) return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or NULL buffer");
+  if (n == 0) return FR_OK;
+  const size_t in_bytes = (size_t)n * height * width * 3, out_bytes = in_bytes * num_augmentations;
+  const uintptr_t ci = (uintptr_t)crops, oi = (uintptr_t)out;
+  if (ci < oi + out_bytes && oi < ci + in_bytes) return fail(h, FR_ERR_INVALID_ARGUMENT, "out overlaps crops");
+  DeviceGuard dg(h->device);
+  AugTables tab;
+  augment_tables(height, width, &tab);
+  const hipError_t e = launch_augment(crops, n, height, width, num_augmentations, tab, out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("augment launch: ") + hipGetErrorString(e));
+  return FR_OK;
 }
 
 int fr_embed_host(fr_handle* h, const uint8_t* rgb, int n, int height, int width, float* out, int normalize) {

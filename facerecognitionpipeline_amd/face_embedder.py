@@ -77,6 +77,7 @@ class FaceEmbedder:
                 state_dict = (load_checkpoint_state_dict(model_path) if model_type == "adaface"
                               else load_arcface_state_dict(model_path, architecture))
         block_specs(architecture)
+        self.max_batch = int(max_batch)  # crops per internal forward chunk (bulk callers chunk by it)
         self.model = _lib.Handle(architecture, model_type, self.device, max_batch)
         self.model.load_state_dict(state_dict)
         self.precision = precision

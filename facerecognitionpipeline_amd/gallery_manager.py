@@ -397,25 +397,28 @@ class GalleryManager:
             self._touch((OP_DELETE, student_id))
             return True
 
-    def add_students_batch(self, entries: Sequence[Tuple[str, str, np.ndarray]], overwrite: bool = False,
+    def add_students_batch(self, entries: Sequence[Tuple], overwrite: bool = False,
                            min_similarity: float = 0.70) -> int:
         """``add_student`` for many students, templates built in one GPU launch
-        (``fr_build_templates``).  ``entries``: (student_id, name, embeddings [n_i,512]).
+        (``fr_build_templates``).  ``entries``: (student_id, name, embeddings [n_i,512]) or
+        (student_id, name, embeddings, metadata) -- ``add_student``'s ``metadata`` (enrollment
+        records its counts there); without it the record gets ``{}``.
         Returns how many were added (existing ids are skipped unless ``overwrite``)."""
         with self._lock:
-            todo = [(sid, name, np.asarray(e, np.float32).reshape(-1, 512)) for sid, name, e in entries
-                    if overwrite or sid not in self.students]
+            todo = [(ent[0], ent[1], np.asarray(ent[2], np.float32).reshape(-1, 512),
+                     (ent[3] if len(ent) > 3 else None) or {}) for ent in entries
+                    if overwrite or ent[0] not in self.students]
             if not todo:
                 return 0
             h = self._get_handle()
             offsets = np.zeros(len(todo) + 1, np.int64)
-            offsets[1:] = np.cumsum([len(e) for _s, _n, e in todo])
-            allemb = torch.from_numpy(np.ascontiguousarray(np.concatenate([e for _s, _n, e in todo]))).to(self.device)
+            offsets[1:] = np.cumsum([len(e) for _s, _n, e, _m in todo])
+            allemb = torch.from_numpy(np.ascontiguousarray(np.concatenate([e for _s, _n, e, _m in todo]))).to(self.device)
             tpl, _kept = h.build_templates(allemb, offsets, self.aggregation_method, min_similarity)
             tpl = tpl.cpu().numpy()
             now = datetime.now().isoformat()
-            for i, (sid, name, e) in enumerate(todo):
-                self.students[sid] = StudentRecord(sid, name, e, tpl[i], len(e), now, now, {})
+            for i, (sid, name, e, meta) in enumerate(todo):
+                self.students[sid] = StudentRecord(sid, name, e, tpl[i], len(e), now, now, meta)
                 self._touch((OP_PUT, sid))
             self._log(f"Added {len(todo)} students (templates built on {self.device})")
             return len(todo)

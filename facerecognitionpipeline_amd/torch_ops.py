@@ -10,6 +10,7 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
     e = torch.ops.frhip.embed(rgb_u8_nhwc, hid, True)        # [N,512] f32
     idx, score = torch.ops.frhip.match_topk(e, hid, 5)       # [N,5] i32 / f32
     idx, score, e = torch.ops.frhip.embed_match(rgb, hid, 5)
+    aug = torch.ops.frhip.augment_faces(crops_u8_nhwc, 8)    # [N,8,H,W,3] u8 (needs no model)
 
 Each op has a fake (meta) implementation, so the ops trace under
 ``torch.fx`` / ``torch.export`` with the right output shapes.
@@ -50,6 +51,24 @@ def _get(hid: int) -> "_lib.Handle":
         return _handles[hid]
     except KeyError:
         raise ValueError(f"frhip handle id {hid} is not registered") from None
+
+
+_utility: Dict[torch.device, "_lib.Handle"] = {}
+
+
+def utility_handle(device) -> "_lib.Handle":
+    """A model-less handle on ``device`` for the entry points that need no weights
+    (``augment_faces``): one per device, created on first use."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    with _lock:
+        h = _utility.get(device)
+        if h is None:
+            h = _utility[device] = _lib.Handle("ir_50", "adaface", device, max_batch=1)
+    return h
 
 
 def _check_rgb(rgb: torch.Tensor, h: "_lib.Handle") -> torch.Tensor:
@@ -108,3 +127,15 @@ def _(rgb, handle, k):
     n = rgb.shape[0]
     return (rgb.new_empty((n, k), dtype=torch.int32), rgb.new_empty((n, k), dtype=torch.float32),
             rgb.new_empty((n, 512), dtype=torch.float32))
+
+
+@torch.library.custom_op("frhip::augment_faces", mutates_args=())
+def augment_faces(crops: torch.Tensor, num_augmentations: int) -> torch.Tensor:
+    if crops.device.type != "cuda":
+        raise ValueError(f"crops are on {crops.device}: augment_faces runs on a HIP device (no CPU fallback)")
+    return utility_handle(crops.device).augment_faces(crops, num_augmentations)
+
+
+@augment_faces.register_fake
+def _(crops, num_augmentations):
+    return crops.new_empty((crops.shape[0], num_augmentations, crops.shape[1], crops.shape[2], 3), dtype=torch.uint8)

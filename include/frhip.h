@@ -85,6 +85,25 @@ int fr_embed_host(fr_handle* h, const uint8_t* rgb, int n, int height, int width
  * [n][112][112][3] uint8. */
 int fr_resize_crops(fr_handle* h, const uint8_t* src, int n, int height, int width, uint8_t* dst, void* stream);
 
+/* augment_face_for_enrollment (enroll_students.py:20-48) for n crops of one size: variant v of crop i,
+ * in the reference's list order, at out[i][v].  v = 0 the crop; 1 cv2.flip(img, 1); 2..5
+ * cv2.warpAffine by getRotationMatrix2D((W/2, H/2), -10 / -5 / 5 / 10, 1.0), INTER_LINEAR,
+ * BORDER_REPLICATE; 6..9 clip(p + beta, 0, 255), beta -20 / -10 / 10 / 20; 10..13
+ * clip(float32(p) * alpha, 0, 255) truncated, alpha 0.85 / 0.92 / 1.08 / 1.15.  Every variant is
+ * uint8-exact; the rotation is pinned to this project's restatement of OpenCV's fixed-point warp
+ * (oracle/align_ref.py: 10-bit map, 5-bit fractions, 15-bit weights, each tap clamped to the
+ * image), not to cv2 itself, which is not a dependency.  The list's entries 14 (cv2.GaussianBlur)
+ * and 15 (unseeded np.random.normal noise) are not implemented: num_augmentations 15 or 16 ->
+ * FR_ERR_UNSUPPORTED; outside [1, 16] -> FR_ERR_INVALID_ARGUMENT.
+ * crops: device uint8 [n][height][width][3] (1 <= height, width <= 8192); out: device uint8
+ * [n][num_augmentations][height][width][3], face-major, so its first two axes flattened are the
+ * reference's all_face_images order (:212-216); out must not overlap crops.  Asynchronous on
+ * `stream`, no host staging; any handle will do, finalised or not (as fr_resize_crops).  n == 0 is
+ * a no-op. */
+#define FR_AUGMENT_MAX 14
+int fr_augment_faces(fr_handle* h, const uint8_t* crops, int n, int height, int width, int num_augmentations,
+                     uint8_t* out, void* stream);
+
 /* Replace the gallery matrix (G rows of D=512 float32).  Replaces the per-query
  * `np.vstack` of GalleryManager.get_gallery_embeddings (gallery_manager.py:177-187):
  * the handle keeps one device-resident copy until the next fr_gallery_set.
