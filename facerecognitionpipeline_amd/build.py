@@ -23,7 +23,8 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = "gfx950"
 SOURCES = ["conv_winograd4.hip", "conv_winograd.hip", "conv_s2.hip", "conv_small.hip","conv_f32_w4.hip", "conv_f32_w8.hip", "conv_bf16x3.hip", "conv_det.hip", "conv_mfma.hip",
-           "embed_misc.hip", "align.hip", "augment.hip", "gallery.hip", "detect.hip", "frhip_runtime.cpp", "detector.cpp"]
+           "embed_misc.hip", "align.hip", "augment.hip", "gallery.hip", "detect.hip", "frhip_runtime.cpp", "finalize.cpp",
+           "conv_dispatch.cpp", "embed_forward.cpp", "align_host.cpp", "frhip_testing.cpp", "detector.cpp"]
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(REPO, "include"), "-I" + CSRC]
 # F(4x4): the input / output transforms are packed f32 where the source says so (explicit f2
@@ -37,9 +38,10 @@ LDFLAGS = ["-shared", f"--offload-arch={ARCH}", f"-Wl,-rpath,{ROCM}/lib", "-Wl,-
 
 def _digest(path: str) -> str:
     h = hashlib.sha256()
-    for p in [path, os.path.join(CSRC, "frhip_kernels.h"), os.path.join(CSRC, "conv_mfma_impl.h"),
-              os.path.join(CSRC, "runtime.h"), os.path.join(CSRC, "warp_map.h"),
-              os.path.join(REPO, "include", "frhip.h"), os.path.join(REPO, "include", "frhip_testing.h")]:
+    # the source and every header it could include: all *.h under csrc/ and include/
+    headers = [os.path.join(d, n) for d in (CSRC, os.path.join(REPO, "include"))
+               for n in sorted(os.listdir(d)) if n.endswith(".h")]
+    for p in [path, *headers]:
         with open(p, "rb") as f:
             h.update(f.read())
     # the flags without this checkout's absolute include paths: the digest (and the build id baked

@@ -347,13 +347,14 @@ int detector_finalize(fr_handle* h) {
   FR_HIP(h, hipMalloc(&d->ws, off));
   d->ws_bytes = off;
   for (auto& p : plan) *p.first = (char*)d->ws + p.second;
-  if (ensure_stream_k(h->device, &h->cus, &h->sk_ws, &h->sk_ws_floats, &h->sk_cnt, &h->sk_cnt_cap) != FR_OK)
+  LaneWs& L = h->lane_ws[0];
+  if (ensure_stream_k(h->device, &h->cus, &L.sk_ws, &L.sk_ws_floats, &L.sk_cnt, &L.sk_cnt_cap) != FR_OK)
     return fail(h, FR_ERR_HIP, "stream-K workspace allocation failed");
   return FR_OK;
 }
 
 // cv::resize INTER_LINEAR coefficient table for one axis: (src0, src1, w0, w1) per output
-// (also the resize branch of FaceEmbedder.preprocess, frhip_runtime.cpp).
+// (also the resize branch of FaceEmbedder.preprocess, embed_forward.cpp resize_device).
 #pragma clang fp contract(off)
 void resize_axis_table(int dsize, int ssize, int* t) {
   const double scale = 1.0 / ((double)dsize / ssize);
@@ -389,7 +390,9 @@ namespace {
 
 int dconv(fr_handle* h, const ConvW& c, const float* x, float* y, int B, int H, int W, Epi epi, const float* res,
           hipStream_t s) {
-  return run_conv(h, c, x, y, B, H, W, epi, res, 0, 0, 1, 0, s);
+  ConvCall call{x, y, B, H, W, epi};
+  call.res = res;
+  return run_conv(h, c, call, h->lane_ws[0], s);
 }
 
 }  // namespace

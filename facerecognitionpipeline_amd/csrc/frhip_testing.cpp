@@ -1,0 +1,329 @@
+// libfrhip test entry points (include/frhip_testing.h): single kernels behind a C call, and the
+// A/B knobs of the conv dispatch and of a handle.  Not part of the public API.
+#include <algorithm>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "runtime.h"
+// (after runtime.h: it declares fr_handle through frhip.h)
+#include "../../include/frhip_testing.h"
+
+using namespace frhip;
+using namespace frhip_rt;
+
+// An A/B knob of a handle: set under its lock; graphs captured with the old value are dropped.
+template <class Set>
+static int set_handle_knob(fr_handle* h, Set set) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard dg(h->device);
+  set();
+  clear_graphs(h);
+  return FR_OK;
+}
+
+extern "C" {
+
+int frt_conv2d(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout, int kh, int kw,
+               int stride, int pad, const float* pre_scale, const float* pre_shift, const float* post_scale,
+               const float* post_shift, const float* prelu, const float* res, int res_h, int res_w, int epi,
+               int nsplit, int tile, int stream_k, int precision, void* stream) {
+  static int t_cus = 0, t_cap = 0;
+  static float* t_ws = nullptr;
+  static long long t_wsf = 0;
+  static int* t_cnt = nullptr;
+  if (epi < 0 || epi > 4 || nsplit < 1 || (nsplit > 1 && epi != EPI_RAW) || (tile < 0 || tile >= TILE_COUNT) ||
+      stride < 1 || kh < 1 || kw < 1 || B < 1)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d: bad arguments");
+  ConvW cw;
+  cw.geometry(cin, cout, kh, kw, stride, pad);
+  ConvParams p = conv_shape(cw, B, H, W, nsplit);
+  p.x = x;
+  p.w = w;
+  p.y = y;
+  p.pre_scale = pre_scale;
+  p.pre_shift = pre_shift;
+  p.post_scale = post_scale;
+  p.post_shift = post_shift;
+  p.prelu = prelu;
+  p.res = res;
+  p.res_H = res_h;
+  p.res_W = res_w;
+  p.split_stride = (long long)p.M * cout;
+  if (stream_k) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (ensure_stream_k(dev, &t_cus, &t_ws, &t_wsf, &t_cnt, &t_cap) != FR_OK)
+      return fail(nullptr, FR_ERR_HIP, "frt_conv2d: stream-K workspace allocation failed");
+    p.sk_cus = t_cus;
+    p.sk_ws = t_ws;
+    p.sk_ws_floats = t_wsf;
+    p.sk_cnt = t_cnt;
+    p.sk_cnt_cap = t_cap;
+  }
+  hipError_t e = launch_conv(p, (ConvTile)tile, pre_scale != nullptr, (Epi)epi, nsplit, (hipStream_t)stream,
+                             precision == 1 ? PREC_BF16X3 : PREC_F32);
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_conv2d_winograd(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout,
+                        const float* pre_scale, const float* pre_shift, const float* post_scale,
+                        const float* post_shift, const float* prelu, const float* res, int epi, void* stream) {
+  if (!wino_supported(cin, cout, 3, 3, 1, 1) || (epi != EPI_AFFINE_PRELU && epi != EPI_AFFINE_RES) ||
+      (epi == EPI_AFFINE_PRELU && (!pre_scale || !pre_shift || !prelu)) || (epi == EPI_AFFINE_RES && (pre_scale || !res)) ||
+      !post_scale || !post_shift || B < 1 || H < 1 || W < 1)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_winograd: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  float* u = nullptr;
+  if (hipMalloc((void**)&u, wino_weight_floats(cout, cin) * sizeof(float)) != hipSuccess)
+    return fail(nullptr, FR_ERR_HIP, "frt_conv2d_winograd: allocation failed");
+  hipError_t e = launch_wino_weights(w, u, cout, cin, s);
+  if (e == hipSuccess) {
+    WinoParams p{};
+    p.x = x;
+    p.u = u;
+    p.y = y;
+    p.pre_scale = pre_scale;
+    p.pre_shift = pre_shift;
+    p.post_scale = post_scale;
+    p.post_shift = post_shift;
+    p.prelu = prelu;
+    p.res = res;
+    p.B = B;
+    p.H = H;
+    p.W = W;
+    p.Cin = cin;
+    p.Cout = cout;
+    e = launch_wino(p, pre_scale != nullptr, (Epi)epi, s);
+  }
+  const hipError_t se = hipStreamSynchronize(s);
+  (void)hipFree(u);
+  if (e == hipSuccess) e = se;
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_winograd: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+static int g_frt_wino4_split = 1;
+int frt_set_wino4_shapes(int mode) {
+  if (mode < 0 || mode > 2) return FR_ERR_INVALID_ARGUMENT;
+  g_knobs.wino4_shapes = mode;
+  return FR_OK;
+}
+int frt_set_wino4_nbg(int nbg) {
+  if (nbg < 0) return FR_ERR_INVALID_ARGUMENT;
+  g_knobs.wino4_nbg = nbg;
+  return FR_OK;
+}
+int frt_set_conv2sc_tile(int tile) {
+  if (tile < -1 || tile >= TILE_COUNT) return FR_ERR_INVALID_ARGUMENT;
+  g_knobs.conv2sc_tile = tile;
+  return FR_OK;
+}
+int frt_set_wino4_max_split(int s) {
+  g_knobs.wino4_max_split = s < 0 ? 0 : s;
+  return FR_OK;
+}
+int frt_conv2d_s2band(const float* x, const float* w, float* y, int B, int H, int W, const float* post_scale,
+                      const float* post_shift, const float* res, void* stream) {
+  if (!s2c64_supported(64, 64, 3, 3, 2, 1, H, W) || B < 1)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_s2band: 64 -> 64 channels, even H, W <= 112");
+  S2Params sp{};
+  sp.x = x;
+  sp.w = w;
+  sp.post_scale = post_scale;
+  sp.post_shift = post_shift;
+  sp.res = res;
+  sp.y = y;
+  sp.B = B;
+  sp.H = H;
+  sp.W = W;
+  const hipError_t e = launch_s2c64(sp, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_s2band: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+int frt_set_s2_band(int on) {
+  g_knobs.s2band = on != 0;
+  return FR_OK;
+}
+int frt_set_wino4_poll_limit(int n) {
+  g_knobs.wino4_poll = n < 0 ? WINO4_POLL_DEFAULT : n;
+  return FR_OK;
+}
+int frt_conv2d_small(const float* x, const float* x2, const float* w, float* y, int B, int H, int W, int cin,
+                     int cin2, int cout, int stride, const float* pre_scale, const float* pre_shift,
+                     const float* post_scale, const float* post_shift, const float* prelu, const float* res, int epi,
+                     void* stream) {
+  if (B < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2) || epi < 0 || epi > 3 || cin2 < 0 ||
+      ((pre_scale != nullptr) != (epi == EPI_AFFINE_PRELU)) || (pre_scale && !pre_shift))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_small: bad arguments");
+  ConvW cw;
+  cw.geometry(cin, cout, 3, 3, stride, 1);
+  cw.cin2 = cin2;
+  ConvParams p = conv_shape(cw, B, H, W);  // (the kernel reads none of the K-step fields)
+  p.x = x;
+  p.x2 = cin2 > 0 ? x2 : nullptr;
+  p.w = w;
+  p.y = y;
+  p.pre_scale = pre_scale;
+  p.pre_shift = pre_shift;
+  p.post_scale = post_scale;
+  p.post_shift = post_shift;
+  p.prelu = prelu;
+  p.res = res;
+  p.res_H = H;
+  p.res_W = W;
+  if (!w || cout % 16 || cin % 16 || cin2 % 16)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_small: bad arguments");
+  // the kernel reads its filters in fragment order: a temporary copy (test entry point)
+  float* wf = nullptr;
+  const size_t wbytes = (size_t)cout * (9 * cin + cin2) * sizeof(float);
+  hipError_t e = hipMalloc((void**)&wf, wbytes);
+  if (e == hipSuccess) e = launch_convs_weights(w, wf, cout, 9 * cin + cin2, (hipStream_t)stream);
+  if (e == hipSuccess) {
+    p.w = wf;
+    e = launch_convs(p, pre_scale != nullptr, (Epi)epi, (hipStream_t)stream);
+  }
+  if (wf) {
+    const hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
+    (void)hipFree(wf);
+    if (e == hipSuccess) e = e2;
+  }
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_small: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+int frt_set_small_conv(fr_handle* h, int max_n) {
+  return set_handle_knob(h, [&] { h->convs_max_n = std::max(0, max_n); });
+}
+int frt_set_small_conv_pre_epilogue(fr_handle* h, int on) {
+  return set_handle_knob(h, [&] { h->convs_pre_epilogue = on != 0; });
+}
+int frt_set_small_conv_pixels(fr_handle* h, int max_m1) {
+  if (!h || max_m1 < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "bad handle or pixel limit");
+  return set_handle_knob(h, [&] { h->convs_max_m1 = max_m1; });
+}
+int frt_set_wino4_blocked(fr_handle* h, int on) {
+  return set_handle_knob(h, [&] { h->w4_blocked = on != 0; });
+}
+int frt_set_small_conv_blocked(fr_handle* h, int on) {
+  return set_handle_knob(h, [&] { h->convs_blocked = on != 0; });
+}
+int frt_set_fuse_shortcut(fr_handle* h, int on) {
+  return set_handle_knob(h, [&] { h->fuse_shortcut = on != 0; });
+}
+int frt_set_wino4_split(int on) {
+  g_frt_wino4_split = on != 0;
+  return FR_OK;
+}
+
+int frt_conv2d_winograd4(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout,
+                        const float* pre_scale, const float* pre_shift, const float* post_scale,
+                        const float* post_shift, const float* prelu, const float* res, int epi, void* stream) {
+  // epilogues: the IR body's (1 with pre-BN, 2) and the detector's (0, 1 without pre-BN, 5)
+  const bool res_epi = epi == EPI_AFFINE_RES || epi == EPI_AFFINE_RES_PRELU;
+  const bool prelu_epi = epi == EPI_AFFINE_PRELU || epi == EPI_AFFINE_RES_PRELU;
+  if (!wino4_supported(cin, cout, 3, 3, 1, 1) ||
+      (epi != EPI_AFFINE && epi != EPI_AFFINE_PRELU && epi != EPI_AFFINE_RES && epi != EPI_AFFINE_RES_PRELU) ||
+      (pre_scale && (epi != EPI_AFFINE_PRELU || !pre_shift)) || (prelu_epi && !prelu) || (res_epi != (res != nullptr)) ||
+      !post_scale || !post_shift || B < 1 || H < 1 || W < 1)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_winograd4: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  ConvW cw;
+  cw.cin = cin;
+  cw.pre_scale = const_cast<float*>(pre_scale);
+  cw.pre_shift = const_cast<float*>(pre_shift);
+  std::vector<float> t;
+  if (hipStreamSynchronize(s) != hipSuccess || !wino4_pre_fold(&cw, t))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_winograd4: pre-BN scale has a zero");
+  float *u = nullptr, *part = nullptr, *pre_t = nullptr;
+  if (hipMalloc((void**)&u, (wino4_weight_floats(cout, cin) + cin) * sizeof(float)) != hipSuccess)
+    return fail(nullptr, FR_ERR_HIP, "frt_conv2d_winograd4: allocation failed");
+  pre_t = u + wino4_weight_floats(cout, cin);
+  hipError_t e = hipMemcpy(pre_t, t.data(), cin * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_wino4_weights(w, pre_scale, u, cout, cin, s);
+  static int* frt_err = nullptr;  // this entry point's device error word (no handle to own one)
+  if (e == hipSuccess && !frt_err) e = hipHostMalloc((void**)&frt_err, sizeof(int), hipHostMallocCoherent | hipHostMallocMapped);
+  if (e == hipSuccess) *(volatile int*)frt_err = 0;
+  if (e == hipSuccess) {
+    Wino4Params p{};
+    p.x = x;
+    p.u = u;
+    p.y = y;
+    p.pre_t = pre_scale ? pre_t : nullptr;
+    p.post_scale = post_scale;
+    p.post_shift = post_shift;
+    p.prelu = prelu;
+    p.res = res;
+    p.B = B;
+    p.H = H;
+    p.W = W;
+    p.Cin = cin;
+    p.Cout = cout;
+    p.no_split = !g_frt_wino4_split;
+    p.poll_max = g_knobs.wino4_poll > 0 ? g_knobs.wino4_poll : -1;
+    p.err = frt_err;
+    p.shapes = g_knobs.wino4_shapes;
+    if (g_frt_wino4_split) {  // split-K partial slots (64 KiB each)
+      p.part_floats = 257ll * 2 * 16 * 16 * 64;
+      if (hipMalloc((void**)&part, p.part_floats * sizeof(float)) != hipSuccess) e = hipErrorOutOfMemory;
+      p.part = part;
+    }
+    if (e == hipSuccess) e = launch_wino4(p, pre_scale != nullptr, (Epi)epi, s);
+  }
+  const hipError_t se = hipStreamSynchronize(s);
+  (void)hipFree(u);
+  (void)hipFree(part);
+  if (e == hipSuccess) e = se;
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_winograd4: ") + hipGetErrorString(e));
+  if (*(volatile int*)frt_err & FR_DEVERR_W4_HANDOFF)
+    return fail(nullptr, FR_ERR_HIP, "frt_conv2d_winograd4: F(4x4) ring hand-off timed out in wino4_kernel");
+  return FR_OK;
+}
+
+int frt_stem(const uint8_t* img, int B, const float* lut, const float* w27x64, const float* bn_scale,
+             const float* bn_shift, const float* prelu, float* y, void* stream) {
+  hipError_t e = launch_stem(img, B, lut, w27x64, bn_scale, bn_shift, prelu, y, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_stem: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_fit_similarity(const float* src, const float* dst, int n, double* M) {
+  if (n < 2 || n > 8) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "n in [2, 8]");
+  return fit_similarity(src, dst, n, M) ? FR_OK : fail(nullptr, FR_ERR_INVALID_ARGUMENT, "similarity fit failed");
+}
+
+int frt_detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int width, float* heads,
+                         uint8_t* canvas, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->detector || !h->finalized) return fail(h, FR_ERR_STATE, "not a finalised detector handle");
+  if (n < 1 || !frames || !heads || height < 2 || width < 2) return fail(h, FR_ERR_INVALID_ARGUMENT, "bad arguments");
+  DeviceGuard dg(h->device);
+  return detector_forward(h, frames, n, height, width, heads, canvas, (hipStream_t)stream);
+}
+
+int frt_set_detector_row_reduction(fr_handle* h, int on) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->detector || !h->det) return fail(h, FR_ERR_STATE, "not a finalised detector handle");
+  detector_set_row_reduction(h->det, on != 0);
+  return FR_OK;
+}
+
+int frt_maxpool3(const float* x, int B, int H, int W, int C, float* y, void* stream) {
+  if (B < 1 || H < 1 || W < 1 || C < 4 || !x || !y)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_maxpool3: bad arguments");
+  const hipError_t e = launch_maxpool3(x, B, H, W, C, y, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_maxpool3: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, void* stream) {
+  if (k < 1 || k > G) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_topk: k must be in [1, G]");
+  hipError_t e = launch_topk(scores, n, G, k, idx, val, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_topk: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+}  // extern "C"

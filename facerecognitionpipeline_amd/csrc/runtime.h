@@ -1,5 +1,12 @@
-// Internals shared by the libfrhip runtime translation units (frhip_runtime.cpp,
-// detector.cpp): the handle, folded-parameter types and the launch helpers.
+// Internals shared by the libfrhip runtime translation units: the handle, folded-parameter types
+// and the launch helpers.
+//   frhip_runtime.cpp  the public fr_* C API (include/frhip.h)
+//   finalize.cpp       handle helpers, state-dict schema, BatchNorm folding, arenas, workspace
+//   conv_dispatch.cpp  run_conv and its kernel-selection rules
+//   embed_forward.cpp  lanes, the layout plan, the IR forward, graphs, resize, gallery match
+//   align_host.cpp     cv2.estimateAffinePartial2D and the augmentation tables (host only)
+//   detector.cpp       the SCRFD detector
+//   frhip_testing.cpp  the frt_* test entry points (include/frhip_testing.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +39,9 @@ struct ConvW {
   float* w_frag = nullptr;   // the serving conv kernel's copy of w in fragment order (launch_convs_weights), or null
   int cin = 0, cout = 0, kh = 0, kw = 0, stride = 1, pad = 0;
   int cin2 = 0;  // fused 1x1 shortcut input channels (w rows KH*KW*cin + cin2 long), else 0
+  void geometry(int cin_, int cout_, int kh_, int kw_, int stride_, int pad_) {
+    cin = cin_, cout = cout_, kh = kh_, kw = kw_, stride = stride_, pad = pad_;
+  }
 };
 
 struct BlockW {
@@ -51,21 +61,59 @@ struct ProfEvent {
   int kind;
 };
 
-// The buffers one running forward writes (a lane).  Lane 0 is the handle's own workspace; lanes
-// 1 .. MAX_LANES - 1 (fr_set_lanes) are further sets, so the parts of a large batch run as
-// concurrent forwards on their own streams and one part's part-empty last round of a layer fills
-// with another part's work.
+// The buffers one running forward writes (a lane).  Lane 0 (fr_finalize, max_batch crops) is also
+// the workspace of every launch outside a forward; lanes 1 .. MAX_LANES - 1 (fr_set_lanes) are
+// further sets, so the parts of a large batch run as concurrent forwards on their own streams and
+// one part's part-empty last round of a layer fills with another part's work.
 struct LaneWs {
   float* act[3] = {nullptr, nullptr, nullptr};
   float* sc_buf = nullptr;
-  float* partial = nullptr;
-  float* w4part = nullptr;
+  float* partial = nullptr;  // head FC split-K parts (fr_handle::HEAD_PARTS x max_batch rows)
+  float* w4part = nullptr;   // F(4x4) split-K partial outputs (small batches), W4PART_FLOATS
+  // stream-K workspace shared by every conv launch of the lane (launches are stream-ordered)
   float* sk_ws = nullptr;
   long long sk_ws_floats = 0;
   int* sk_cnt = nullptr;
   int sk_cnt_cap = 0;
 };
 constexpr int MAX_LANES = 4;
+
+// What one run_conv launch reads and writes.
+struct ConvCall {
+  const float* x;
+  float* y;
+  int B, H, W;
+  frhip::Epi epi;
+  const float* res = nullptr;
+  int res_H = 0, res_W = 0;
+  const float* x2 = nullptr;  // the fused shortcut's input (cw.cin2 > 0)
+  int nsplit = 1;             // split-K slices, split_stride elements apart
+  long long split_stride = 0;
+  // channel-blocked layout bits of this launch (plan_layouts): CONVS_BLK_* for the serving conv
+  // kernel (ConvParams::blk), W4_BLK_* for the F(4x4) kernel (Wino4Params::blk)
+  int convs_blk = 0, w4_blk = 0;
+  // serving conv kernel only: also write y * y2_scale + y2_shift, the next block's pre-BN input
+  float* y2 = nullptr;
+  const float *y2_scale = nullptr, *y2_shift = nullptr;
+};
+
+// Process-wide A/B knobs of the conv dispatch (set through frt_set_*; conv_dispatch.cpp).
+struct ConvKnobs {
+  // frt_set_conv2sc_tile: the tile of the fused stride-2 conv2 + conv-shortcut launches, -1 = the rule
+  int conv2sc_tile = -1;
+  // frt_set_wino4_nbg: tile blocks per XCD item group of the F(4x4) launches, 0 = the rule
+  int wino4_nbg = 0;
+  // cap on the F(4x4) split-K parts of small grids (frt_set_wino4_max_split: serving sweeps); 0 = none
+  int wino4_max_split = 0;
+  // the stage-1 stride-2 conv2 on its band kernel (frt_set_s2_band: tests compare it with the
+  // implicit-GEMM kernel)
+  int s2band = 1;
+  // poll bound of wino4_kernel's ring hand-off waits (frt_set_wino4_poll_limit: tests force expiry)
+  int wino4_poll = frhip::WINO4_POLL_DEFAULT;
+  // F(4x4) item shapes for layers of 65..96 and of <= 32 couts (frt_set_wino4_shapes: A/B and tests)
+  int wino4_shapes = 1;
+};
+extern ConvKnobs g_knobs;
 
 struct Detector;  // detector.cpp
 void detector_destroy(Detector* d);
@@ -78,8 +126,8 @@ void detector_convs(Detector* d, std::vector<ConvW*>& out);
 struct fr_handle {
   std::mutex mu;
   std::string arch, model_type, err;
-  bool arcface = false;
-  bool detector = false;  // arch "scrfd_10g": a face detector, not an embedding model  // insightface IResNet keys/semantics (face_embedder.py:64-88)
+  bool arcface = false;   // insightface IResNet keys/semantics (face_embedder.py:64-88)
+  bool detector = false;  // arch "scrfd_10g": a face detector, not an embedding model
   int device = 0;
   int max_batch = 256;
   bool finalized = false;
@@ -95,10 +143,7 @@ struct fr_handle {
   frhip_rt::ConvW head;  // BN2d pre-affine + FC as 7x7 valid conv
   float *fc_bias = nullptr, *bn1d_scale = nullptr, *bn1d_shift = nullptr;
 
-  // workspace
-  float *act[3] = {nullptr, nullptr, nullptr};
-  float* sc_buf = nullptr;
-  float* partial = nullptr;
+  // workspace (activations, partials and the stream-K slabs: lane_ws below)
   // head FC split-K parts: serving batches (4 n <= max_batch) / larger; partial buffers hold
   // HEAD_PARTS x max_batch rows (>= 98 n for the serving split at 4 n <= max_batch, >= 32 n for the other)
   static constexpr int HEAD_SPLIT_SMALL = 98, HEAD_SPLIT = 32, HEAD_PARTS = 49;
@@ -144,12 +189,7 @@ struct fr_handle {
   void* blur_ws = nullptr;  // multi-block blur: per (image, chunk) int64 L sums + double values
   size_t blur_ws_cap = 0;
 
-  // stream-K workspace shared by every body conv launch (launches are stream-ordered)
-  int cus = 0;
-  float* sk_ws = nullptr;
-  long long sk_ws_floats = 0;
-  int* sk_cnt = nullptr;
-  int sk_cnt_cap = 0;
+  int cus = 0;  // CUs of the device (ensure_stream_k)
   bool stream_k = true;
   bool fuse_shortcut = true;  // conv2 + conv shortcut as one launch (frt_set_fuse_shortcut: A/B)
   frhip::Precision prec = frhip::PREC_F32;
@@ -158,12 +198,10 @@ struct fr_handle {
   float* wino_arena = nullptr;   // F(2x2) filters, built when that algorithm is selected
   float* wino4_arena = nullptr;  // F(4x4) filters, likewise
   float* convs_arena = nullptr;  // the serving conv kernel's filters (ConvW::w_frag), built at fr_finalize
-  float* w4part = nullptr;         // F(4x4) split-K partial outputs (small batches), W4PART_FLOATS
   static constexpr long long W4PART_FLOATS = 16ll << 20;
 
   // lanes (fr_set_lanes): a forward of n crops runs as min(lane_max, n / lane_min) concurrent
-  // parts, lane 0 on the caller's stream with the workspace above, lane l >= 1 on lane_stream[l]
-  // with lane_ws[l]
+  // parts with workspace lane_ws[l], lane 0 on the caller's stream, lane l >= 1 on lane_stream[l]
   int lane_min = 0, lane_max = 1;
   bool lanes_fallback = false;  // lanes were turned off by a failed lane-workspace allocation
   frhip_rt::LaneWs lane_ws[frhip_rt::MAX_LANES];
@@ -192,20 +230,15 @@ struct fr_handle {
   int convs_max_n = 2;
   // output-pixel limit of a batch-1 layer on that kernel (frt_set_small_conv_pixels; batch 2: 1,024)
   int convs_max_m1 = 4096;
-  // a one-lane forward's conv2 on that kernel also writes the next block's pre-BN input into
-  // convs_y2 (forward_lanes sets these three; run_conv sets convs_y2_done when it did), and that
-  // block's conv1 then runs without pre-BN on it (frt_set_small_conv_pre_epilogue: A/B)
-  float* convs_y2 = nullptr;
-  const float *convs_y2_scale = nullptr, *convs_y2_shift = nullptr;
-  bool convs_y2_done = false;
+  // a one-lane forward's conv2 on that kernel also writes the next block's pre-BN input
+  // (ConvCall::y2), and that block's conv1 then runs without pre-BN on it
+  // (frt_set_small_conv_pre_epilogue: A/B)
   bool convs_pre_epilogue = true;
   // activations passed between two serving-kernel layers of a one-lane forward are channel-blocked
-  // (ConvParams::blk; forward_lanes sets convs_blk per launch); frt_set_small_conv_blocked: A/B
-  int convs_blk = 0;
+  // (ConvCall::convs_blk, from plan_layouts); frt_set_small_conv_blocked: A/B
   bool convs_blocked = true;
-  // channel-blocked activations between F(4x4) layers of larger forwards (forward_lanes sets w4_blk,
-  // the Wino4Params::blk of the next launch); frt_set_wino4_blocked: A/B
-  int w4_blk = 0;
+  // channel-blocked activations between F(4x4) layers of larger forwards (ConvCall::w4_blk, from
+  // plan_layouts); frt_set_wino4_blocked: A/B
   bool w4_blocked = true;
 
   // device-side error word (host-pinned, coherent): kernels that detect a broken invariant
@@ -230,7 +263,7 @@ struct fr_handle {
     for (auto& g : graphs) (void)hipGraphExecDestroy(g.exec);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (lane_fork) (void)hipEventDestroy(lane_fork);
-    for (int l = 1; l < frhip_rt::MAX_LANES; ++l) {
+    for (int l = 0; l < frhip_rt::MAX_LANES; ++l) {  // (lane 0 has no stream / event of its own)
       if (lane_stream[l]) (void)hipStreamDestroy(lane_stream[l]);
       if (lane_join[l]) (void)hipEventDestroy(lane_join[l]);
       frhip_rt::LaneWs& L = lane_ws[l];
@@ -245,10 +278,6 @@ struct fr_handle {
     (void)hipFree(wino_arena);
     (void)hipFree(wino4_arena);
     (void)hipFree(convs_arena);
-    (void)hipFree(w4part);
-    for (auto p : act) (void)hipFree(p);
-    (void)hipFree(sc_buf);
-    (void)hipFree(partial);
     (void)hipFree(in_stage);
     (void)hipFree(emb_stage);
     for (auto& t : rs_tabs) {
@@ -263,8 +292,6 @@ struct fr_handle {
     (void)hipFree(match_io);
     (void)hipFree(gallery_tmp);
     (void)hipFree(tpl_offsets);
-    (void)hipFree(sk_ws);
-    (void)hipFree(sk_cnt);
     (void)hipFree(align_m);
     (void)hipFree(blur_out);
     (void)hipFree(blur_ws);
@@ -319,12 +346,59 @@ void bn_fold(const std::vector<float>* gamma, const std::vector<float>* beta, co
 std::vector<float> repack_oihw(const std::vector<float>& w, int O, int I, int kh, int kw);
 int ensure_buf(fr_handle* h, void** p, size_t* cap, size_t bytes);
 int ensure_stream_k(int device, int* cus, float** ws, long long* ws_floats, int** cnt, int* cnt_cap);
-// L: the lane whose stream-K / split-K workspace the launch uses (nullptr: the handle's own)
-// x2: the fused shortcut's input (cw.cin2 > 0)
-int run_conv(fr_handle* h, const ConvW& cw, const float* x, float* y, int B, int H, int W, frhip::Epi epi,
-             const float* res, int res_H, int res_W, int nsplit, long long split_stride, hipStream_t s,
-             const LaneWs* L = nullptr, const float* x2 = nullptr);
 const std::vector<float>* getp(fr_handle* h, const std::string& k);
+
+// finalize.cpp
+extern thread_local std::string g_create_error;  // fail(nullptr, ...): fr_last_error(NULL)
+std::vector<BlockSpec> block_specs(const std::string& arch, bool* ok);
+std::map<std::string, size_t> embedder_schema(bool arcface, const std::vector<BlockSpec>& specs);
+// t = pre_shift / pre_scale per input channel of c (zeros without pre-BN); false if not finite
+bool wino4_pre_fold(const ConvW* c, std::vector<float>& t);
+// the filters of the selected Winograd algorithm, built on first use after fr_finalize
+int ensure_winograd(fr_handle* h);
+// fr_finalize under the handle's lock and device: fold, upload, allocate the workspace
+int finalize_model(fr_handle* h);
+
+// conv_dispatch.cpp
+// The geometry and K-step fields of conv cw over a B x H x W input in nsplit K-slices: what the
+// kernel-selection rules read, and every non-pointer field a launch needs.
+frhip::ConvParams conv_shape(const ConvW& cw, int B, int H, int W, int nsplit = 1);
+// Whether run_conv puts a launch on the serving conv kernel / the F(4x4) kernel: one rule each
+// for run_conv's branches and for plan_layouts, so the two cannot disagree.
+bool convs_takes(const fr_handle* h, const ConvW& cw, frhip::ConvParams p, frhip::Epi epi, int nsplit, bool has_x2);
+bool w4_takes(const fr_handle* h, const ConvW& cw, frhip::Epi epi, int res_H, int res_W, int Ho, int Wo);
+// One conv launch on stream s with lane L's stream-K / split-K workspace.  *wrote_y2 is set when
+// the launch wrote c.y2 (only the serving conv kernel does).
+int run_conv(fr_handle* h, const ConvW& cw, const ConvCall& c, const LaneWs& L, hipStream_t s,
+             bool* wrote_y2 = nullptr);
+
+// embed_forward.cpp
+// Times the launches of its scope with a pair of events when profiling is on (fr_profile_enable).
+struct ProfScope {
+  fr_handle* h;
+  hipStream_t s;
+  ProfEvent ev{};
+  bool on;
+  ProfScope(fr_handle* h_, hipStream_t s_, double flop, int kind, double exec_flop = -1.0);
+  ~ProfScope();
+};
+void clear_graphs(fr_handle* h);
+int forward_staged(fr_handle* h, int n, int normalize, hipStream_t s);
+int embed_device(fr_handle* h, const uint8_t* rgb, int n, float* out, int normalize, hipStream_t s);
+int resize_device(fr_handle* h, const uint8_t* src, int n, int H, int W, uint8_t* dst, hipStream_t s);
+int check_crop_size(fr_handle* h, int height, int width);
+int embed_any(fr_handle* h, const uint8_t* rgb, int n, int height, int width, float* out, int normalize,
+              hipStream_t s);
+int match_device(fr_handle* h, const float* Q, int n, int k, int32_t* idx, float* score, hipStream_t s);
+// Grow the gallery allocation to hold `rows` rows, keeping the first G rows (stream-ordered).
+int gallery_reserve(fr_handle* h, int rows, hipStream_t s);
+
+// align_host.cpp
+// estimateAffinePartial2D(src, dst)[0]: returns false (M NaN) where cv2 returns None
+bool fit_similarity(const float* src, const float* dst, int n, double M[6]);
+void invert_affine(const double Mf[6], double Mi[6]);
+void augment_tables(int H, int W, frhip::AugTables* t);
+void reference_template(int S, float t[10]);
 
 // detector.cpp
 // cv::resize INTER_LINEAR (uint8) coefficient table of one axis: (src0, src1, w0, w1) per output

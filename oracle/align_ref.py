@@ -24,7 +24,7 @@ source semantics; tests pin the HIP kernels to THIS restatement bit for bit.
   pivoting instead of ``DECOMP_EIG``, and sums run in index order.  (OpenCV
   4.7+ rewrote the LM solver; on this linear model every variant converges to
   the inliers' least-squares optimum.)  The C++ fit behind ``fr_align_faces``
-  (frhip_runtime.cpp) performs the same IEEE operation sequence.
+  (csrc/align_host.cpp) performs the same IEEE operation sequence.
 * ``invert_affine``: warpAffine's double-precision inverse (imgwarp.cpp).
 * ``warp_affine_linear``: warpAffine INTER_LINEAR, BORDER_CONSTANT 0, uint8:
   AB_BITS=10 fixed-point map (cvRound = round-half-even), INTER_BITS=5 sub-pixel

@@ -5,7 +5,7 @@ kernel instances allow (GPU).
 
 usage: python tools/det_conv_sweep.py [--frames 32] [--reps 10] [--sk 1]
 Prints per layer: microseconds per launch for each tile, and the runtime's current choice (the
-detector branch of the tile rule in frhip_runtime.cpp run_conv).  Conv + BN + ReLU (epi 1 without
+detector branch of the tile rule in conv_dispatch.cpp run_conv).  Conv + BN + ReLU (epi 1 without
 pre-BN) runs on the detector's own instance set (conv_det.hip: tiles 128x64w8, 128x128w8,
 256x128w8); conv + BN (epi 0) and conv + BN + residual (epi 2) on the network's sets.
 """
