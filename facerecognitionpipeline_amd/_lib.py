@@ -42,6 +42,7 @@ _SIGNATURES = {
     "fr_gallery_delete_rows": (_I, [_P, _I, _I, _P]),
     "fr_gallery_read": (_I, [_P, _I, _I, _P, _I, _P]),
     "fr_build_templates": (_I, [_P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P]),
+    "fr_track_consensus": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_double, _I, ctypes.c_double, _P, _P, _P]),
     "fr_match_topk": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "fr_match_topk_host": (_I, [_P, _P, _I, _I, _P, _P]),
     "fr_embed_match": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
@@ -239,6 +240,31 @@ class Handle:
                     emb: Optional[torch.Tensor] = None) -> None:
         check(self._lib.fr_embed_match(self.h, ptr(rgb), rgb.shape[0], int(k), ptr(idx), ptr(score), ptr(emb),
                                        stream_of(self.device)), self.h)
+
+    def track_consensus(self, idx: torch.Tensor, score: torch.Tensor, offsets, min_quality: float = 0.55,
+                        min_frames: int = 3, similarity_threshold: float = 0.5):
+        """The reference's track vote (``FaceMatcher._aggregate_matches`` / ``_get_best_candidate``)
+        for len(offsets)-1 tracks whose frames are CSR rows of the device top-k output ``idx`` int32 /
+        ``score`` float32 [total,k] -> (int32 [T,8] = status, winner row, winner count, pool size,
+        second count, frames, quality frames, 0; float64 [T,2] = confidence, ratio) on the device."""
+        import numpy as np
+        if (idx.dim() != 2 or idx.dtype != torch.int32 or score.dtype != torch.float32
+                or tuple(score.shape) != tuple(idx.shape)):
+            raise ValueError("expected idx int32 [total,k] and score float32 [total,k]")
+        if idx.device != self.device or score.device != self.device:
+            raise ValueError(f"idx / score are on {idx.device} / {score.device}, the handle on {self.device} "
+                             "(no CPU fallback)")
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        T = off.shape[0] - 1
+        if T < 0 or (T > 0 and int(off[-1]) != idx.shape[0]):
+            raise ValueError(f"offsets must end at the {idx.shape[0]} rows of idx / score")
+        idx, score = idx.contiguous(), score.contiguous()
+        out_i = torch.empty((T, 8), dtype=torch.int32, device=self.device)
+        out_d = torch.empty((T, 2), dtype=torch.float64, device=self.device)
+        check(self._lib.fr_track_consensus(self.h, ptr(idx), ptr(score), idx.shape[1], off.ctypes.data, T,
+                                           float(min_quality), int(min_frames), float(similarity_threshold),
+                                           ptr(out_i), ptr(out_d), stream_of(self.device)), self.h)
+        return out_i, out_d
 
     # -- alignment / quality ----------------------------------------------
     def align_faces(self, frame: torch.Tensor, landmarks, out_size: int, out: torch.Tensor):

@@ -257,6 +257,22 @@ enum TemplateMethod : int { TEMPLATE_MEAN = 0, TEMPLATE_MEDIAN = 1, TEMPLATE_WEI
 hipError_t launch_templates(const float* emb, const int* offsets, int n_students, int method, float min_sim,
                             float* out, int* kept, hipStream_t s);
 
+// Track consensus (track.hip: FaceMatcher._aggregate_matches / _get_best_candidate) of n_tracks CSR
+// slices of the top-k output idx / score [total][k] (column 0 is read); offsets: device
+// [n_tracks + 1], 1..TRACK_MAX_FRAMES frames each; out_i: [n_tracks][8] = status, winner row,
+// winner count, pool size, second count, frames, quality frames, 0; out_d: [n_tracks][2] =
+// confidence, ratio.
+constexpr int TRACK_MAX_FRAMES = 1024;
+enum TrackStatus : int {
+  TRACK_RECOGNIZED = 0,
+  TRACK_FEW_FRAMES = 1,
+  TRACK_NO_CONSENSUS = 2,
+  TRACK_BELOW_THRESHOLD = 3
+};
+hipError_t launch_track_consensus(const int* idx, const float* score, int k, const int* offsets, int n_tracks,
+                                  double min_quality, int min_frames, double similarity_threshold, int* out_i,
+                                  double* out_d, hipStream_t s);
+
 // ---- SCRFD detector glue (detect.hip)
 constexpr int DET_MAX_CANDIDATES = 4096;  // per frame, above det_thresh, before NMS
 

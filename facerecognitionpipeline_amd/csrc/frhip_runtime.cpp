@@ -271,6 +271,39 @@ int fr_build_templates(fr_handle* h, const float* emb, const int32_t* offsets, i
   return FR_OK;
 }
 
+int fr_track_consensus(fr_handle* h, const int32_t* idx, const float* score, int k, const int32_t* offsets,
+                       int n_tracks, double min_quality, int min_frames, double similarity_threshold,
+                       int32_t* out_i, double* out_d, void* stream) {
+  // the argument checks need no handle and come first: they report the same way for h == NULL
+  std::unique_lock<std::mutex> lk;
+  if (h) lk = std::unique_lock<std::mutex>(h->mu);
+  if (n_tracks < 0 || (n_tracks > 0 && (!idx || !score || !offsets || !out_i || !out_d)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n_tracks or NULL buffer");
+  if (k < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "k must be >= 1");
+  if (min_frames < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "min_frames must be >= 1");
+  if (n_tracks > 0 && offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
+  for (int i = 0; i < n_tracks; ++i) {
+    const long long n = (long long)offsets[i + 1] - offsets[i];
+    if (n < 1 || n > TRACK_MAX_FRAMES)
+      return fail(h, FR_ERR_INVALID_ARGUMENT,
+                  "every track needs 1.." + std::to_string(TRACK_MAX_FRAMES) + " frames (track " +
+                      std::to_string(i) + " has " + std::to_string(n) + ")");
+  }
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  if (n_tracks == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ob = (size_t)(n_tracks + 1) * sizeof(int32_t);
+  int rc = ensure_buf(h, &h->tpl_offsets, &h->tpl_offsets_cap, ob);
+  if (rc) return rc;
+  FR_HIP(h, hipMemcpyAsync(h->tpl_offsets, offsets, ob, hipMemcpyHostToDevice, s));
+  hipError_t e = launch_track_consensus(idx, score, k, (const int*)h->tpl_offsets, n_tracks, min_quality, min_frames,
+                                        similarity_threshold, out_i, out_d, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("track consensus launch: ") + hipGetErrorString(e));
+  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
+  return FR_OK;
+}
+
 int fr_gallery_size(fr_handle* h, int* G) {
   if (!h || !G) return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL argument");
   std::lock_guard<std::mutex> lk(h->mu);

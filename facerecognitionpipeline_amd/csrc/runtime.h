@@ -178,7 +178,7 @@ struct fr_handle {
   size_t match_io_cap = 0;
   void* gallery_tmp = nullptr;  // tail staging for row deletes
   size_t gallery_tmp_cap = 0;
-  void* tpl_offsets = nullptr;  // CSR offsets of fr_build_templates
+  void* tpl_offsets = nullptr;  // CSR offsets of fr_build_templates / fr_track_consensus (both synchronise)
   size_t tpl_offsets_cap = 0;
 
   // alignment / quality workspace

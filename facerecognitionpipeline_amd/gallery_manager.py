@@ -451,20 +451,28 @@ class GalleryManager:
         ``(sid, name, score)`` -- all under the gallery lock, so a concurrent mutation can
         neither change the rows between the match and their resolution nor make two threads
         replay one delta twice."""
+        return self.match_resolved_with(n, top_k, launch, None)[0]
+
+    def match_resolved_with(self, n: int, top_k: int, launch, on_device):
+        """:meth:`match_resolved`, and ``on_device(handle, idx, score)`` on the filled device
+        tensors before they are copied out (e.g. the track vote on the resident top-k), under the
+        same lock -> ``(results, on_device's return value)``; the value is None when nothing was
+        matched (empty gallery, ``top_k`` selecting no row, n == 0) or ``on_device`` is None."""
         with self._lock:
             if not self.students:
-                return [[] for _ in range(n)]
+                return [[] for _ in range(n)], None
             k = _slice_len(len(self.students), top_k)
             if k == 0 or n == 0:
-                return [[] for _ in range(n)]
+                return [[] for _ in range(n)], None
             h = self._sync_device()
             idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
             score = torch.empty((n, k), dtype=torch.float32, device=self.device)
             launch(h, k, idx, score)
+            extra = on_device(h, idx, score) if on_device is not None else None
             idx, score = idx.cpu().numpy(), score.cpu().numpy()
             ids = self._ids
             return [[(ids[i], self.students[ids[i]].name, float(s)) for i, s in zip(ri, rs)]
-                    for ri, rs in zip(idx, score)]
+                    for ri, rs in zip(idx, score)], extra
 
     def search_device(self, queries: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device form: float32 [n,512] on the GPU -> (int32 [n,k] gallery rows, float32 [n,k] scores).

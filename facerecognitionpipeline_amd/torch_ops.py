@@ -11,6 +11,7 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
     idx, score = torch.ops.frhip.match_topk(e, hid, 5)       # [N,5] i32 / f32
     idx, score, e = torch.ops.frhip.embed_match(rgb, hid, 5)
     aug = torch.ops.frhip.augment_faces(crops_u8_nhwc, 8)    # [N,8,H,W,3] u8 (needs no model)
+    rec_i, rec_d = torch.ops.frhip.track_consensus(idx, score, offsets, 0.55, 3, 0.5)  # [T,8] i32 / [T,2] f64
 
 Each op has a fake (meta) implementation, so the ops trace under
 ``torch.fx`` / ``torch.export`` with the right output shapes.
@@ -19,7 +20,7 @@ from __future__ import annotations
 
 import itertools
 import threading
-from typing import Dict, Tuple
+from typing import Dict, List, Tuple
 
 import torch
 
@@ -58,7 +59,7 @@ _utility: Dict[torch.device, "_lib.Handle"] = {}
 
 def utility_handle(device) -> "_lib.Handle":
     """A model-less handle on ``device`` for the entry points that need no weights
-    (``augment_faces``): one per device, created on first use."""
+    (``augment_faces``, ``track_consensus``): one per device, created on first use."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
@@ -139,3 +140,18 @@ def augment_faces(crops: torch.Tensor, num_augmentations: int) -> torch.Tensor:
 @augment_faces.register_fake
 def _(crops, num_augmentations):
     return crops.new_empty((crops.shape[0], num_augmentations, crops.shape[1], crops.shape[2], 3), dtype=torch.uint8)
+
+
+@torch.library.custom_op("frhip::track_consensus", mutates_args=())
+def track_consensus(idx: torch.Tensor, score: torch.Tensor, offsets: List[int], min_quality: float,
+                    min_frames: int, similarity_threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    if idx.device.type != "cuda":
+        raise ValueError(f"idx is on {idx.device}: track_consensus runs on a HIP device (no CPU fallback)")
+    return utility_handle(idx.device).track_consensus(idx, score, offsets, min_quality, min_frames,
+                                                      similarity_threshold)
+
+
+@track_consensus.register_fake
+def _(idx, score, offsets, min_quality, min_frames, similarity_threshold):
+    t = max(len(offsets) - 1, 0)
+    return idx.new_empty((t, 8), dtype=torch.int32), idx.new_empty((t, 2), dtype=torch.float64)

@@ -148,6 +148,37 @@ int fr_match_topk_host(fr_handle* h, const float* Q, int n, int k, int32_t* idx,
 int fr_embed_match(fr_handle* h, const uint8_t* rgb, int n, int k, int32_t* idx, float* score, float* emb_out,
                    void* stream);
 
+/* FaceMatcher._aggregate_matches and _get_best_candidate (face_matcher.py:321-385) for n_tracks
+ * tracks in one launch, on the top-k output of fr_match_topk / fr_embed_match while it is on the
+ * device.  idx / score: device [total][k] (k >= 1; only column 0, each frame's top-1, is read; a
+ * gallery row stands for its student id); track t = frames [offsets[t], offsets[t+1]) (host offsets,
+ * offsets[0] = 0, 1..FR_TRACK_MAX_FRAMES frames each).  Per track:
+ *   quality frame  (double)score >= min_quality (the reference's 0.55)
+ *   pool           the quality frames, or all frames when there is none
+ *   winner         the row with the most pool frames; equal counts: the row whose first pool frame
+ *                  comes earliest (Counter.most_common order); second = the next row in that order
+ *   ratio          winner_count / pool_size;  confidence = mean of the winner's pool scores (double)
+ *   consensus      ratio > 0.5, or with a second row: ratio > 0.4 && winner_count >= 2 * second_count
+ *   status         FR_TRACK_FEW_FRAMES if quality_frames < min_frames (the reference's 3), else
+ *                  FR_TRACK_NO_CONSENSUS, else FR_TRACK_BELOW_THRESHOLD if confidence <
+ *                  similarity_threshold, else FR_TRACK_RECOGNIZED
+ * out_i[t] = {status, winner_row, winner_count, pool_size, second_count, n_frames, quality_frames, 0};
+ * out_d[t] = {confidence, ratio}.  The winner over the pool is both _aggregate_matches' winner and
+ * _get_best_candidate's candidate, so one record serves both.  Deterministic: integer votes, the
+ * confidence summed in double in one fixed order.  Any handle will do, finalised or not (as
+ * fr_resize_crops).  Synchronises (the offsets are staged from the host).  n_tracks == 0 is a
+ * no-op; NULL buffers, k < 1, min_frames < 1, offsets[0] != 0 and an empty or over-long track ->
+ * FR_ERR_INVALID_ARGUMENT (checked before the handle, so also reported for h == NULL). */
+#define FR_TRACK_RECOGNIZED 0
+#define FR_TRACK_FEW_FRAMES 1 /* fewer than min_frames quality frames */
+#define FR_TRACK_NO_CONSENSUS 2
+#define FR_TRACK_BELOW_THRESHOLD 3
+#define FR_TRACK_MAX_FRAMES 1024
+int fr_track_consensus(fr_handle* h, const int32_t* idx, const float* score, int k, const int32_t* offsets,
+                       int n_tracks, double min_quality, int min_frames, double similarity_threshold,
+                       int32_t* out_i /* device [n_tracks][8] */, double* out_d /* device [n_tracks][2] */,
+                       void* stream);
+
 /* FaceAligner.align for n faces of one frame (face_recognition.py:50-75): similarity fit of
  * each face's 5 landmarks to the reference template (cv2.estimateAffinePartial2D semantics,
  * host, double) then warpAffine INTER_LINEAR / BORDER_CONSTANT 0 on the device, so the crops

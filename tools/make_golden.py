@@ -55,6 +55,14 @@ the reference's own ``face_embedder.FaceEmbedder`` and
   with ``add_student`` (samples + metadata) from
   ``gallery/backups/adaface_ir_101_backup_*.json`` and ``.save()``d.  Its
   templates and search results are those of ``backup_adaface_ir_101.npz``.
+* ``track_consensus.npz`` — the reference ``FaceMatcher._aggregate_matches`` /
+  ``_get_best_candidate`` (face_matcher.py:321-385), called unbound with a stand-in ``self``
+  that carries only ``similarity_threshold``, on hand-built tracks (majorities, the 0.4 / 0.5
+  ratio edges, ties in both orders, too few or no quality frames, the f32 neighbours of 0.55,
+  tracks of 1 / 255 / 256 / 257 / 1024 frames): per group of one (k, threshold) the top-k
+  ``idx`` / ``score`` / ``offsets`` a launch takes (columns past 0 are decoys) and per track the
+  reference's outputs and the FR_TRACK_* status they imply; and the reference
+  ``_generate_summary`` (:446-477) of all those tracks' results.
 
 Two modules the reference imports are absent from this image and are supplied
 in a temporary directory that is put on ``sys.path`` for this run only:
@@ -66,7 +74,7 @@ fixture).  Weights are the seeded synthetic checkpoint of
 format.  Crops are regenerated from their seeds at test time; their SHA-256 is
 stored to pin them.
 
-Usage: ``python tools/make_golden.py [embed] [c3] [resize] [backups] [refpkl] [gate] [image] [dropin]``
+Usage: ``python tools/make_golden.py [embed] [c3] [resize] [backups] [refpkl] [gate] [image] [track] [dropin]``
 (no argument: all).
 """
 from __future__ import annotations
@@ -178,7 +186,8 @@ def quiet():
 def main() -> None:
     if not os.path.isdir(REF):
         raise SystemExit("reference not present; golden files are generated in the build container only")
-    parts = set(sys.argv[1:]) or {"embed", "c3", "resize", "backups", "refpkl", "gate", "image", "dropin"}
+    parts = set(sys.argv[1:]) or {"embed", "c3", "resize", "backups", "refpkl", "gate", "image", "track",
+                                     "dropin"}
     os.makedirs(OUT, exist_ok=True)
     tmp = tempfile.mkdtemp(prefix="frgolden_")
     with open(os.path.join(tmp, "cv2.py"), "w") as f:
@@ -410,6 +419,110 @@ def main() -> None:
         np.savez_compressed(os.path.join(OUT, "image.npz"), decoded_sha256=np.array(json.dumps(want)),
                             process_image=np.array(json.dumps(runs)), missing_error=np.array(missing))
         print("image", {k: len(v) for k, v in runs.items()}, missing)
+
+    if "track" in parts:
+        import types
+        import face_matcher as ref_fm  # reference module (cv2 / net stubbed above)
+        A, B, C, D, E, F = 99999, 7, 31337, 0, 512, 65536  # gallery rows; A: the last row of a 100k gallery
+        f32 = np.float32
+        below = np.nextafter(f32(0.55), f32(0))  # the f32 just under f32(0.55)
+        assert float(f32(0.55)) >= 0.55 > float(below)
+        q = [0.80, 0.70, 0.75, 0.60, 0.66, 0.91, 0.58, 0.62, 0.73, 0.69, 0.77]
+        R, FEW, NOC, BEL = 0, 1, 2, 3  # FR_TRACK_* as the issue states them per case
+        # (label, k, similarity_threshold, rows, scores, status)
+        cases = [
+            ("01_majority", 1, 0.5, [A, A, A, B], q[:4], R),
+            ("02_5_2_1_1_1_1", 3, 0.5, [A, B, A, C, A, D, B, A, E, F, A], q[:11], R),
+            ("03_4_2_1_1_1_1_ratio_0.4", 1, 0.5, [A, B, A, C, A, D, B, A, E, F], q[:10], NOC),
+            ("04_2_1_1_second_rule", 3, 0.5, [A, B, A, C], q[:4], R),
+            ("05_tie_aabb", 1, 0.5, [A, A, B, B], q[:4], NOC),
+            ("05_tie_baab", 3, 0.5, [B, A, A, B], q[:4], NOC),
+            ("06_3_2_ratio_0.6", 1, 0.5, [B, A, B, A, B], q[:5], R),
+            ("07_three_quality_frames", 3, 0.5, [B, A, A, B, A, B], [0.30, 0.60, 0.70, 0.20, 0.65, 0.54], R),
+            ("08_two_quality_frames", 1, 0.5, [B, A, B, A, B], [0.50, 0.70, 0.40, 0.60, 0.30], FEW),
+            ("09_no_quality_frames", 3, 0.5, [B, A, B, A, B, C], [-0.10, 1e-30, 0.30, 0.54, 1e-8, -0.999], FEW),
+            ("10_below_threshold", 3, 0.6, [A, A, B, A, A], [0.56, 0.57, 0.90, 0.58, 0.57], BEL),
+            ("11_edge_quality", 1, 0.5, [A, A, A], [f32(0.55)] * 3, R),
+            ("11_edge_below", 1, 0.5, [A, A, A], [f32(0.55), f32(0.55), below], FEW),
+        ]
+        r = np.random.Generator(np.random.PCG64(0xFACE07AC))
+        for n in (1, 255, 256, 257, 1024):  # block-stride sizes: seeded rows of 3 ids, scores about 0.55
+            p = [0.45, 0.35, 0.2] if n in (255, 256) else [0.6, 0.25, 0.15]
+            cases.append((f"12_len_{n}", 1 if n % 2 else 3, 0.5, r.choice([A, B, C], size=n, p=p).tolist(),
+                          r.uniform(0.45, 0.95, size=n).astype(f32).tolist(), None))
+
+        def stand_in(thr):  # the two vote functions read nothing of self but the threshold
+            return types.SimpleNamespace(similarity_threshold=thr)
+
+        def frame_matches(rows, scores):
+            return [{"frame": f"{i:06d}.jpg", "student_id": f"S{row:06d}", "name": f"N{row}", "score": float(f32(s))}
+                    for i, (row, s) in enumerate(zip(rows, scores))]
+
+        groups = sorted({(k, thr) for _l, k, thr, _r, _s, _st in cases})
+        out = {"labels": np.array([c[0] for c in cases]), "n_groups": np.int32(len(groups)),
+               "min_quality": np.float64(0.55), "min_frames": np.int32(3)}
+        results = []  # match_track-shaped results of every track, for _generate_summary
+        for g, (k, thr) in enumerate(groups):
+            mine = [c for c in cases if (c[1], c[2]) == (k, thr)]
+            total = sum(len(c[3]) for c in mine)
+            idx = np.zeros((total, k), np.int32)
+            score = np.zeros((total, k), f32)
+            rec = {n: [] for n in ("agg_none", "status", "row", "confidence", "consensus_strength",
+                                   "num_quality_frames", "total_frames_evaluated", "cand_row", "cand_confidence",
+                                   "cand_num_quality_frames")}
+            at = 0
+            offsets = [0]
+            for label, _k, _thr, rows, scores, want in mine:
+                n = len(rows)
+                idx[at:at + n, 0] = rows
+                score[at:at + n, 0] = np.asarray(scores, f32)
+                for c in range(1, k):  # decoys in the other columns: a vote that read them would differ
+                    idx[at:at + n, c] = (np.asarray(rows) + 13 * c) % 100000
+                    score[at:at + n, c] = score[at:at + n, 0] * f32(1.0 - 0.05 * c)
+                at += n
+                offsets.append(at)
+                fm = frame_matches(rows, scores)
+                with quiet():
+                    agg = ref_fm.FaceMatcher._aggregate_matches(stand_in(thr), fm, {})
+                    cand = ref_fm.FaceMatcher._get_best_candidate(stand_in(thr), fm, {})
+                    loose = ref_fm.FaceMatcher._aggregate_matches(stand_in(-np.inf), fm, {})
+                nq = sum(m["score"] >= 0.55 for m in fm)
+                status = R if agg is not None else BEL if loose is not None else FEW if nq < 3 else NOC
+                assert want is None or status == want, (label, status, want)
+                rec["agg_none"].append(agg is None)
+                rec["status"].append(status)
+                rec["row"].append(int(agg["student_id"][1:]) if agg else -1)
+                rec["confidence"].append(agg["confidence"] if agg else np.nan)
+                rec["consensus_strength"].append(agg["consensus_strength"] if agg else np.nan)
+                rec["num_quality_frames"].append(agg["num_quality_frames"] if agg else -1)
+                rec["total_frames_evaluated"].append(agg["total_frames_evaluated"] if agg else -1)
+                rec["cand_row"].append(int(cand["student_id"][1:]))
+                rec["cand_confidence"].append(cand["confidence"])
+                rec["cand_num_quality_frames"].append(cand["num_quality_frames"])
+                if agg is not None:
+                    results.append({"track_id": label, "recognized": True, "student_id": agg["student_id"],
+                                    "name": agg["name"], "confidence": agg["confidence"]})
+                else:
+                    results.append({"track_id": label, "recognized": False, "reason": "below_threshold",
+                                    "best_candidate": cand})
+                print("track", label, "k", k, "thr", thr, "status", status, "cand", cand["student_id"],
+                      cand["confidence"])
+            out[f"g{g}_labels"] = np.array([c[0] for c in mine])
+            out[f"g{g}_k"] = np.int32(k)
+            out[f"g{g}_similarity_threshold"] = np.float64(thr)
+            out[f"g{g}_idx"], out[f"g{g}_score"] = idx, score
+            out[f"g{g}_offsets"] = np.asarray(offsets, np.int32)
+            for name, v in rec.items():
+                out[f"g{g}_{name}"] = np.asarray(v)
+        n_rec = sum(x["recognized"] for x in results)
+        me = types.SimpleNamespace(similarity_threshold=0.5, aggregation_method="consensus")
+        summary = ref_fm.FaceMatcher._generate_summary(me, results, n_rec, len(results) - n_rec)
+        empty = ref_fm.FaceMatcher._generate_summary(me, [], 0, 0)
+        out["summary_results"] = np.array(json.dumps(results))
+        out["summary_ref"] = np.array(json.dumps(summary))
+        out["summary_ref_empty"] = np.array(json.dumps(empty))
+        np.savez_compressed(os.path.join(OUT, "track_consensus.npz"), **out)
+        print("track", len(cases), "tracks in", len(groups), "groups;", n_rec, "recognized")
 
     if "dropin" in parts:
         import shutil
