@@ -8,8 +8,8 @@ fallback.
 """
 from .arch import block_specs, flop_per_face, state_dict_schema  # noqa: F401
 
-__all__ = ["FaceEmbedder", "GalleryManager", "FaceMatcher", "StudentEnrollment", "block_specs", "flop_per_face",
-           "state_dict_schema"]
+__all__ = ["FaceEmbedder", "GalleryManager", "FaceMatcher", "StudentEnrollment", "SimpleTracker", "FrameAccumulator",
+           "CameraFaceCapture", "block_specs", "flop_per_face", "state_dict_schema"]
 
 
 def __getattr__(name):
@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == "StudentEnrollment":
         from .enroll_students import StudentEnrollment
         return StudentEnrollment
+    if name in ("SimpleTracker", "FrameAccumulator", "CameraFaceCapture"):
+        from . import face_detection
+        return getattr(face_detection, name)
     raise AttributeError(name)

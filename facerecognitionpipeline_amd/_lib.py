@@ -43,6 +43,8 @@ _SIGNATURES = {
     "fr_gallery_read": (_I, [_P, _I, _I, _P, _I, _P]),
     "fr_build_templates": (_I, [_P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P]),
     "fr_track_consensus": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_double, _I, ctypes.c_double, _P, _P, _P]),
+    "fr_capture_tracks": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_double, _I, ctypes.c_double, _I, _P, _P, _P,
+                               _P, _P]),
     "fr_match_topk": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "fr_match_topk_host": (_I, [_P, _P, _I, _I, _P, _P]),
     "fr_embed_match": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
@@ -265,6 +267,53 @@ class Handle:
                                            float(min_quality), int(min_frames), float(similarity_threshold),
                                            ptr(out_i), ptr(out_d), stream_of(self.device)), self.h)
         return out_i, out_d
+
+    def capture_tracks(self, bbox: torch.Tensor, metrics: torch.Tensor, valid: torch.Tensor, frame_offsets,
+                       clip_offsets=None, max_disappeared: int = 30, max_distance: float = 50,
+                       target_frames: int = 12, min_quality_score: float = 0.5, save_partial: bool = False,
+                       raise_on_clip_error: bool = True):
+        """The reference's ``SimpleTracker.update`` + ``FrameAccumulator`` (face_detection.py:11-228)
+        for len(clip_offsets)-1 capture sessions in one launch.  ``bbox`` int32 [total,4], ``metrics``
+        float64 [total,5] (det_score, blur_score, yaw, pitch, roll) and ``valid`` uint8 / bool [total]
+        on the device; frame f = detections [frame_offsets[f], frame_offsets[f+1]), clip c = frames
+        [clip_offsets[c], clip_offsets[c+1]) (default: one clip of all frames) -> (track_id int32
+        [total], quality float64 [total], slot int32 [total], clip_info int32 [C,4] = tracks opened,
+        tracks completed, frames saved, error) on the device.  A clip past the kernel's limits raises
+        NotImplementedError; with ``raise_on_clip_error=False`` the outputs are returned instead and
+        ``clip_info[:, 3]`` names the clips (their track_id is 0 and slot -1 throughout)."""
+        import numpy as np
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        if (bbox.dim() != 2 or bbox.shape[1] != 4 or bbox.dtype != torch.int32 or metrics.dtype != torch.float64
+                or tuple(metrics.shape) != (bbox.shape[0], 5) or valid.dtype != torch.uint8
+                or tuple(valid.shape) != (bbox.shape[0],)):
+            raise ValueError("expected bbox int32 [total,4], metrics float64 [total,5] and valid uint8 [total]")
+        for name, x in (("bbox", bbox), ("metrics", metrics), ("valid", valid)):
+            if x.device != self.device:
+                raise ValueError(f"{name} is on {x.device}, the handle on {self.device} (no CPU fallback)")
+        fo = np.ascontiguousarray(frame_offsets, dtype=np.int32).reshape(-1)
+        if fo.shape[0] < 1:
+            raise ValueError("frame_offsets needs at least its leading 0")
+        co = np.ascontiguousarray([0, fo.shape[0] - 1] if clip_offsets is None else clip_offsets,
+                                  dtype=np.int32).reshape(-1)
+        C = co.shape[0] - 1
+        if C < 0 or (C > 0 and int(co[-1]) != fo.shape[0] - 1):
+            raise ValueError(f"clip_offsets must end at the {fo.shape[0] - 1} frames of frame_offsets")
+        if int(fo[-1]) != bbox.shape[0]:
+            raise ValueError(f"frame_offsets must end at the {bbox.shape[0]} rows of bbox / metrics / valid")
+        bbox, metrics, valid = bbox.contiguous(), metrics.contiguous(), valid.contiguous()
+        total = bbox.shape[0]
+        track_id = torch.empty((total,), dtype=torch.int32, device=self.device)
+        quality = torch.empty((total,), dtype=torch.float64, device=self.device)
+        slot = torch.empty((total,), dtype=torch.int32, device=self.device)
+        info = torch.empty((max(C, 0), 4), dtype=torch.int32, device=self.device)
+        rc = self._lib.fr_capture_tracks(self.h, ptr(bbox), ptr(metrics), ptr(valid), fo.ctypes.data, co.ctypes.data,
+                                         C, int(max_disappeared), float(max_distance), int(target_frames),
+                                         float(min_quality_score), int(bool(save_partial)), ptr(track_id),
+                                         ptr(quality), ptr(slot), ptr(info), stream_of(self.device))
+        if rc != FR_ERR_UNSUPPORTED or raise_on_clip_error:
+            check(rc, self.h)
+        return track_id, quality, slot, info
 
     # -- alignment / quality ----------------------------------------------
     def align_faces(self, frame: torch.Tensor, landmarks, out_size: int, out: torch.Tensor):

@@ -273,6 +273,23 @@ hipError_t launch_track_consensus(const int* idx, const float* score, int k, con
                                   double min_quality, int min_frames, double similarity_threshold, int* out_i,
                                   double* out_d, hipStream_t s);
 
+// Capture sessions (capture.hip: SimpleTracker.update + FrameAccumulator) of n_clips CSR slices: clip c
+// = frames [clip_off[c], clip_off[c+1]), frame f = detections [frame_off[f], frame_off[f+1]) of bbox
+// [total][4] / metrics [total][5] / valid [total]; both offset arrays on the device, at most
+// CAPTURE_MAX_FACES detections per frame and CAPTURE_MAX_DETS per clip.  q_limit: the smallest 4 x
+// squared centroid distance that is no match.  track_id / quality / slot: [total]; clip_info:
+// [n_clips][4] = tracks opened, tracks completed, frames saved, CAPTURE_ERR_* (0: none).
+constexpr int CAPTURE_MAX_FACES = 128;
+constexpr int CAPTURE_MAX_TRACKS = 128;
+constexpr int CAPTURE_MAX_DETS = 4096;
+constexpr int CAPTURE_MAX_TARGET = 64;
+constexpr int CAPTURE_COORD_MAX = 1 << 20;
+enum CaptureError : int { CAPTURE_ERR_TRACKS = 1, CAPTURE_ERR_COORD = 2 };
+hipError_t launch_capture_tracks(const int* bbox, const double* metrics, const unsigned char* valid,
+                                 const int* frame_off, const int* clip_off, int n_clips, int max_disappeared,
+                                 long long q_limit, int target_frames, double min_quality_score, int save_partial,
+                                 int* track_id, double* quality, int* slot, int* clip_info, hipStream_t s);
+
 // ---- SCRFD detector glue (detect.hip)
 constexpr int DET_MAX_CANDIDATES = 4096;  // per frame, above det_thresh, before NMS
 

@@ -3,6 +3,7 @@
 // reference code each replaces).  The gallery rows kept in HBM here replace
 //   GalleryManager.get_gallery_embeddings   gallery_manager.py:177-187 (A10)
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -12,6 +13,20 @@
 
 using namespace frhip;
 using namespace frhip_rt;
+
+namespace frhip_rt {
+
+long long capture_q_limit(double max_distance) {
+  if (!(max_distance > 0.0)) return 0;  // also NaN: `distances.min() < nan` is never true
+  // past every q in range (q <= 2^45: coordinates within +-FR_CAPTURE_COORD_MAX)
+  if (max_distance >= 4194304.0) return 1ll << 46;
+  long long q = (long long)std::floor(4.0 * max_distance * max_distance);
+  while (q > 0 && std::sqrt((double)(q - 1) / 4.0) >= max_distance) --q;
+  while (std::sqrt((double)q / 4.0) < max_distance) ++q;
+  return q;
+}
+
+}  // namespace frhip_rt
 
 extern "C" {
 
@@ -301,6 +316,76 @@ int fr_track_consensus(fr_handle* h, const int32_t* idx, const float* score, int
                                         similarity_threshold, out_i, out_d, s);
   if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("track consensus launch: ") + hipGetErrorString(e));
   FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
+  return FR_OK;
+}
+
+int fr_capture_tracks(fr_handle* h, const int32_t* bbox, const double* metrics, const uint8_t* valid,
+                      const int32_t* frame_offsets, const int32_t* clip_offsets, int n_clips, int max_disappeared,
+                      double max_distance, int target_frames, double min_quality_score, int save_partial,
+                      int32_t* track_id, double* quality, int32_t* slot, int32_t* clip_info, void* stream) {
+  // the argument checks need no handle and come first: they report the same way for h == NULL
+  std::unique_lock<std::mutex> lk;
+  if (h) lk = std::unique_lock<std::mutex>(h->mu);
+  if (n_clips < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "n_clips must be >= 0");
+  if (target_frames < 1 || target_frames > CAPTURE_MAX_TARGET)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "target_frames must be in [1, " + std::to_string(CAPTURE_MAX_TARGET) + "]");
+  if (max_disappeared < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "max_disappeared must be >= 0");
+  int n_frames = 0, total = 0;
+  if (n_clips > 0) {
+    if (!frame_offsets || !clip_offsets) return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer (offsets)");
+    if (clip_offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "clip_offsets[0] must be 0");
+    if (frame_offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "frame_offsets[0] must be 0");
+    for (int c = 0; c < n_clips; ++c)
+      if (clip_offsets[c + 1] < clip_offsets[c])
+        return fail(h, FR_ERR_INVALID_ARGUMENT, "clip_offsets decrease at clip " + std::to_string(c));
+    n_frames = clip_offsets[n_clips];
+    for (int f = 0; f < n_frames; ++f) {
+      const long long n = (long long)frame_offsets[f + 1] - frame_offsets[f];
+      if (n < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "frame_offsets decrease at frame " + std::to_string(f));
+      if (n > CAPTURE_MAX_FACES)
+        return fail(h, FR_ERR_INVALID_ARGUMENT,
+                    "a frame holds at most " + std::to_string(CAPTURE_MAX_FACES) + " detections (frame " +
+                        std::to_string(f) + " has " + std::to_string(n) + ")");
+    }
+    for (int c = 0; c < n_clips; ++c) {
+      const long long n = (long long)frame_offsets[clip_offsets[c + 1]] - frame_offsets[clip_offsets[c]];
+      if (n > CAPTURE_MAX_DETS)
+        return fail(h, FR_ERR_INVALID_ARGUMENT,
+                    "a clip holds at most " + std::to_string(CAPTURE_MAX_DETS) + " detections (clip " +
+                        std::to_string(c) + " has " + std::to_string(n) + ")");
+    }
+    total = frame_offsets[n_frames];
+    if (!clip_info || (total > 0 && (!bbox || !metrics || !valid || !track_id || !quality || !slot)))
+      return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer");
+  }
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  if (n_clips == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  // frame offsets, then clip offsets, in one staging buffer
+  std::vector<int32_t> off(frame_offsets, frame_offsets + n_frames + 1);
+  off.insert(off.end(), clip_offsets, clip_offsets + n_clips + 1);
+  const size_t ob = off.size() * sizeof(int32_t);
+  int rc = ensure_buf(h, &h->tpl_offsets, &h->tpl_offsets_cap, ob);
+  if (rc) return rc;
+  FR_HIP(h, hipMemcpyAsync(h->tpl_offsets, off.data(), ob, hipMemcpyHostToDevice, s));
+  const int* d_off = (const int*)h->tpl_offsets;
+  hipError_t e = launch_capture_tracks(bbox, metrics, valid, d_off, d_off + n_frames + 1, n_clips, max_disappeared,
+                                       capture_q_limit(max_distance), target_frames, min_quality_score,
+                                       save_partial != 0, track_id, quality, slot, clip_info, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("capture tracks launch: ") + hipGetErrorString(e));
+  std::vector<int32_t> info((size_t)n_clips * 4);
+  FR_HIP(h, hipMemcpyAsync(info.data(), clip_info, info.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
+  for (int c = 0; c < n_clips; ++c) {
+    const int err = info[(size_t)c * 4 + 3];
+    if (err)
+      return fail(h, FR_ERR_UNSUPPORTED,
+                  "clip " + std::to_string(c) +
+                      (err == CAPTURE_ERR_TRACKS
+                           ? ": more than " + std::to_string(CAPTURE_MAX_TRACKS) + " tracks alive at once"
+                           : ": a box coordinate beyond +-" + std::to_string(CAPTURE_COORD_MAX)));
+  }
   return FR_OK;
 }
 

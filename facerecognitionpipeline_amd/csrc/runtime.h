@@ -178,7 +178,8 @@ struct fr_handle {
   size_t match_io_cap = 0;
   void* gallery_tmp = nullptr;  // tail staging for row deletes
   size_t gallery_tmp_cap = 0;
-  void* tpl_offsets = nullptr;  // CSR offsets of fr_build_templates / fr_track_consensus (both synchronise)
+  // CSR offsets of fr_build_templates / fr_track_consensus / fr_capture_tracks (all synchronise)
+  void* tpl_offsets = nullptr;
   size_t tpl_offsets_cap = 0;
 
   // alignment / quality workspace
@@ -358,6 +359,12 @@ bool wino4_pre_fold(const ConvW* c, std::vector<float>& t);
 int ensure_winograd(fr_handle* h);
 // fr_finalize under the handle's lock and device: fold, upload, allocate the workspace
 int finalize_model(fr_handle* h);
+
+// frhip_runtime.cpp
+// fr_capture_tracks' match threshold: the smallest integer q >= 0 with sqrt(q / 4.0) >= max_distance
+// in double (q = 4 x a squared centroid distance), so that q < q_limit is the reference's
+// `distance < max_distance`; 0 for max_distance <= 0 or NaN
+long long capture_q_limit(double max_distance);
 
 // conv_dispatch.cpp
 // The geometry and K-step fields of conv cw over a B x H x W input in nsplit K-slices: what the

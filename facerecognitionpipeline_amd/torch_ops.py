@@ -12,6 +12,8 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
     idx, score, e = torch.ops.frhip.embed_match(rgb, hid, 5)
     aug = torch.ops.frhip.augment_faces(crops_u8_nhwc, 8)    # [N,8,H,W,3] u8 (needs no model)
     rec_i, rec_d = torch.ops.frhip.track_consensus(idx, score, offsets, 0.55, 3, 0.5)  # [T,8] i32 / [T,2] f64
+    tid, quality, slot, info = torch.ops.frhip.capture_tracks(bbox, metrics, valid, frame_offsets, clip_offsets,
+                                                              30, 80.0, 12, 0.5, False)  # [N] x 3, [C,4] i32
 
 Each op has a fake (meta) implementation, so the ops trace under
 ``torch.fx`` / ``torch.export`` with the right output shapes.
@@ -59,7 +61,7 @@ _utility: Dict[torch.device, "_lib.Handle"] = {}
 
 def utility_handle(device) -> "_lib.Handle":
     """A model-less handle on ``device`` for the entry points that need no weights
-    (``augment_faces``, ``track_consensus``): one per device, created on first use."""
+    (``augment_faces``, ``track_consensus``, ``capture_tracks``): one per device, created on first use."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
@@ -155,3 +157,23 @@ def track_consensus(idx: torch.Tensor, score: torch.Tensor, offsets: List[int], 
 def _(idx, score, offsets, min_quality, min_frames, similarity_threshold):
     t = max(len(offsets) - 1, 0)
     return idx.new_empty((t, 8), dtype=torch.int32), idx.new_empty((t, 2), dtype=torch.float64)
+
+
+@torch.library.custom_op("frhip::capture_tracks", mutates_args=())
+def capture_tracks(bbox: torch.Tensor, metrics: torch.Tensor, valid: torch.Tensor, frame_offsets: List[int],
+                   clip_offsets: List[int], max_disappeared: int, max_distance: float, target_frames: int,
+                   min_quality_score: float, save_partial: bool
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    if bbox.device.type != "cuda":
+        raise ValueError(f"bbox is on {bbox.device}: capture_tracks runs on a HIP device (no CPU fallback)")
+    return utility_handle(bbox.device).capture_tracks(bbox, metrics, valid, frame_offsets, clip_offsets,
+                                                      max_disappeared, max_distance, target_frames,
+                                                      min_quality_score, save_partial)
+
+
+@capture_tracks.register_fake
+def _(bbox, metrics, valid, frame_offsets, clip_offsets, max_disappeared, max_distance, target_frames,
+      min_quality_score, save_partial):
+    n, c = bbox.shape[0], max(len(clip_offsets) - 1, 0)
+    return (bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((n,), dtype=torch.float64),
+            bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((c, 4), dtype=torch.int32))

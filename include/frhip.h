@@ -179,6 +179,61 @@ int fr_track_consensus(fr_handle* h, const int32_t* idx, const float* score, int
                        int32_t* out_i /* device [n_tracks][8] */, double* out_d /* device [n_tracks][2] */,
                        void* stream);
 
+/* Capture sessions: SimpleTracker.update and FrameAccumulator (face_detection.py:11-228) with the
+ * is_valid test of CameraFaceCapture.process_frame (:271-283) for n_clips independent sessions
+ * (cameras) in one launch.  Each session starts from an empty tracker with next_track_id = 1.
+ * Detections are a CSR over frames, frames a CSR over clips; the number of frames is
+ * clip_offsets[n_clips] and the number of detections frame_offsets[that].
+ *   tracker   The live tracks are an ordered list (the reference's dict order): a matched track keeps
+ *             its place, deleted tracks leave with the order of the rest kept, new tracks are appended
+ *             in detection order.  Per track x detection pair q = (sx_t - sx_d)^2 + (sy_t - sy_d)^2
+ *             with sx = x1 + x2, sy = y1 + y2 in int64: 4 x the squared centroid distance, exact.
+ *             Greedy matching takes the unmatched pair of smallest q, ties to the smallest flat
+ *             index track_pos * n_dets + det_idx (numpy's argmin), until no unmatched pair has
+ *             q < q_limit; q_limit is the smallest integer q >= 0 with sqrt(q / 4.0) >= max_distance
+ *             in double, so the test is the reference's `distances.min() < max_distance` bit for bit
+ *             (max_distance <= 0 or NaN: no pair matches).  A matched track takes the detection's box
+ *             and disappeared = 0; an unmatched one gets disappeared += 1 and is deleted when that
+ *             exceeds max_disappeared; every unmatched detection opens a track with the next id.
+ *   quality   nb = min(blur / 200.0, 1.0); pose = max(0, 1.0 - (|yaw| / 90.0 + |pitch| / 90.0 +
+ *             |roll| / 90.0) / 3.0); quality = det * 0.4 + nb * 0.3 + pose * 0.3, in double in this
+ *             order without contraction (compute_quality_score); metrics must be finite.
+ *   saving    A detection passes when valid != 0 and !(quality < min_quality_score).  A track accepts
+ *             its first target_frames passing detections in frame order; with target_frames of them
+ *             it is completed and they are saved, with fewer they are saved only if save_partial != 0
+ *             (the reference's 's' key, then quitting).  slot = the rank among the track's accepted
+ *             frames by descending quality, equal qualities in frame order (Python's stable
+ *             sort(reverse=True)): the NNN of frame_NNN.jpg; -1 for everything that is not saved.
+ * clip_info[c] = {tracks opened, tracks completed, frames saved, error}.  A clip whose live tracks
+ * would exceed FR_CAPTURE_MAX_TRACKS (error FR_CAPTURE_ERR_TRACKS) or with a coordinate beyond
+ * +-FR_CAPTURE_COORD_MAX (FR_CAPTURE_ERR_COORD) gets {0, 0, 0, error}, track_id 0 and slot -1
+ * throughout (its qualities are still written), the other clips their results, and the call returns
+ * FR_ERR_UNSUPPORTED after its synchronisation.  Deterministic: integers but for the quality.  Any
+ * handle will do, finalised or not.  Synchronises (the offsets are staged from the host).
+ * n_clips == 0 is a no-op.  NULL buffers, n_clips < 0, offsets that do not start at 0 or that
+ * decrease, a frame over FR_CAPTURE_MAX_FACES, a clip over FR_CAPTURE_MAX_DETS, target_frames outside
+ * [1, FR_CAPTURE_MAX_TARGET] and max_disappeared < 0 -> FR_ERR_INVALID_ARGUMENT (checked before the
+ * handle, so also reported for h == NULL). */
+#define FR_CAPTURE_MAX_FACES 128  /* detections in one frame */
+#define FR_CAPTURE_MAX_TRACKS 128 /* tracks alive at once in one clip */
+#define FR_CAPTURE_MAX_DETS 4096  /* detections in one clip */
+#define FR_CAPTURE_MAX_TARGET 64  /* target_frames */
+#define FR_CAPTURE_COORD_MAX (1 << 20)
+#define FR_CAPTURE_ERR_TRACKS 1
+#define FR_CAPTURE_ERR_COORD 2
+int fr_capture_tracks(fr_handle* h,
+                      const int32_t* bbox,          /* device [total][4] x1 y1 x2 y2 (bbox.astype(int)) */
+                      const double* metrics,        /* device [total][5] det_score, blur_score, yaw, pitch, roll */
+                      const uint8_t* valid,         /* device [total] face['is_valid'] */
+                      const int32_t* frame_offsets, /* host [n_frames + 1] */
+                      const int32_t* clip_offsets,  /* host [n_clips + 1] */
+                      int n_clips, int max_disappeared, double max_distance, int target_frames,
+                      double min_quality_score, int save_partial,
+                      int32_t* track_id, /* device [total] >= 1 */
+                      double* quality,   /* device [total] */
+                      int32_t* slot,     /* device [total] */
+                      int32_t* clip_info /* device [n_clips][4] */, void* stream);
+
 /* FaceAligner.align for n faces of one frame (face_recognition.py:50-75): similarity fit of
  * each face's 5 landmarks to the reference template (cv2.estimateAffinePartial2D semantics,
  * host, double) then warpAffine INTER_LINEAR / BORDER_CONSTANT 0 on the device, so the crops

@@ -74,7 +74,16 @@ fixture).  Weights are the seeded synthetic checkpoint of
 format.  Crops are regenerated from their seeds at test time; their SHA-256 is
 stored to pin them.
 
-Usage: ``python tools/make_golden.py [embed] [c3] [resize] [backups] [refpkl] [gate] [image] [track] [dropin]``
+* ``capture_tracks.npz`` — the reference ``SimpleTracker`` and ``FrameAccumulator``
+  (face_detection.py:11-228), driven as ``CameraFaceCapture.process_frame`` drives them (:271-283),
+  on hand-built and seeded synthetic sessions (``tests/_capture_cases.py`` builds them: ties in
+  both directions, the ``max_distance`` and ``max_disappeared`` edges, deletions and returns, empty
+  frames, quality edges, partial tracks with and without the forced save): per session the boxes,
+  metrics, validity, frame offsets and settings a launch takes, and the reference's track id,
+  ``compute_quality_score`` and saved ``frame_NNN`` number of every detection and the
+  ``metadata.json`` numbers of every saved track.  scipy (``cdist``) is the installed one.
+
+Usage: ``python tools/make_golden.py [embed] [c3] [resize] [backups] [refpkl] [gate] [image] [track] [capture] [dropin]``
 (no argument: all).
 """
 from __future__ import annotations
@@ -156,6 +165,12 @@ def imread(path, flags=1):
             return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8)[..., ::-1])
     except (OSError, ValueError, SyntaxError):
         return None
+def imwrite(path, img):
+    # face_detection.py's save_track (capture fixture): BGR in, written through PIL (bytes unpinned)
+    import numpy as np
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(img[..., ::-1])).save(path, quality=95)
+    return True
 def Laplacian(gray, ddepth):
     import numpy as np
     assert ddepth == CV_64F
@@ -187,7 +202,7 @@ def main() -> None:
     if not os.path.isdir(REF):
         raise SystemExit("reference not present; golden files are generated in the build container only")
     parts = set(sys.argv[1:]) or {"embed", "c3", "resize", "backups", "refpkl", "gate", "image", "track",
-                                     "dropin"}
+                                     "capture", "dropin"}
     os.makedirs(OUT, exist_ok=True)
     tmp = tempfile.mkdtemp(prefix="frgolden_")
     with open(os.path.join(tmp, "cv2.py"), "w") as f:
@@ -523,6 +538,67 @@ def main() -> None:
         out["summary_ref_empty"] = np.array(json.dumps(empty))
         np.savez_compressed(os.path.join(OUT, "track_consensus.npz"), **out)
         print("track", len(cases), "tracks in", len(groups), "groups;", n_rec, "recognized")
+
+    if "capture" in parts:
+        import face_detection as ref_fd  # reference module (cv2 / insightface stubbed above; scipy is real)
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        import _capture_cases as CC
+        from facerecognitionpipeline_amd.face_detection import capture_tracks_host
+
+        def ref_quality(m):
+            acc = ref_fd.FrameAccumulator.__new__(ref_fd.FrameAccumulator)  # compute_quality_score reads no state
+            return acc.compute_quality_score({"det_score": float(m[0]), "quality_metrics": {
+                "blur_score": float(m[1]), "yaw": float(m[2]), "pitch": float(m[3]), "roll": float(m[4])}})
+
+        edge = ref_quality(CC.EDGE)
+        assert type(edge) is float, type(edge)
+        built = CC.build_sessions(edge)
+        out = {"n_sessions": np.int32(len(built))}
+        reached = set()
+        for s, sess in enumerate(built):
+            bbox, metrics, valid, offsets = CC.arrays(sess)
+            assert 12 <= len(offsets) - 1 <= 40 and max(np.diff(offsets)) <= 8, (s, len(offsets) - 1)
+            d = {"bbox": bbox, "metrics": metrics, "valid": valid, "frame_offsets": offsets}
+            tracker = ref_fd.SimpleTracker(max_disappeared=sess["max_disappeared"], max_distance=sess["max_distance"])
+            with quiet():
+                acc = ref_fd.FrameAccumulator(target_frames=sess["target_frames"],
+                                              min_quality_score=sess["min_quality_score"],
+                                              output_dir=os.path.join(tmp, f"capture_{s}"))
+                ids = CC.drive(tracker, acc, d, bool(sess["save_partial"]))
+            quality = np.array([ref_quality(m) for m in metrics], dtype=np.float64)
+            slot = CC.saved_slots(acc, len(valid))
+            meta = [acc.metadata[t] for t in sorted(acc.metadata)]
+            for m in meta:  # the folder the reference wrote
+                track_dir = os.path.join(tmp, f"capture_{s}", f"track_{m['track_id']:03d}")
+                assert sorted(os.listdir(track_dir)) == m["files"] + ["metadata.json"], track_dir
+            trace = set()
+            params = {k: sess[k] for k in CC.PARAMS}
+            h_ids, h_quality, h_slot, h_info = capture_tracks_host(bbox, metrics, valid, offsets, trace=trace, **params)
+            # the host statement of the kernel's contract is the reference, or the fixture is not written
+            assert np.array_equal(h_ids, ids) and np.array_equal(h_slot, slot), s
+            assert h_quality.tobytes() == quality.tobytes(), s
+            assert h_info == [tracker.next_track_id - 1, sum(m["num_frames"] == sess["target_frames"] for m in meta),
+                              int((slot >= 0).sum()), 0], (s, h_info)
+            reached |= trace
+            for name, v in (("track_id", ids), ("quality", quality), ("slot", slot),
+                            ("n_tracks", np.int32(tracker.next_track_id - 1)),
+                            ("meta_track_id", np.array([m["track_id"] for m in meta], np.int32)),
+                            ("meta_num_frames", np.array([m["num_frames"] for m in meta], np.int32)),
+                            ("meta_avg_quality", np.array([m["avg_quality"] for m in meta], np.float64)),
+                            ("meta_avg_det_score", np.array([m["avg_det_score"] for m in meta], np.float64)),
+                            ("max_disappeared", np.int32(sess["max_disappeared"])),
+                            ("max_distance", np.float64(sess["max_distance"])),
+                            ("target_frames", np.int32(sess["target_frames"])),
+                            ("min_quality_score", np.float64(sess["min_quality_score"])),
+                            ("save_partial", np.int32(sess["save_partial"]))):
+                d[name] = v
+            for name, v in d.items():
+                out[f"s{s}_{name}"] = v
+            print("capture session", s, "frames", len(offsets) - 1, "detections", len(valid), "tracks",
+                  tracker.next_track_id - 1, "saved", sorted(acc.metadata), sorted(trace))
+        assert reached >= CC.REQUIRED, sorted(CC.REQUIRED - reached)
+        np.savez_compressed(os.path.join(OUT, "capture_tracks.npz"), **out)
+        print("capture", len(built), "sessions;", os.path.getsize(os.path.join(OUT, "capture_tracks.npz")), "bytes")
 
     if "dropin" in parts:
         import shutil
