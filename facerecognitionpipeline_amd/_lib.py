@@ -45,6 +45,8 @@ _SIGNATURES = {
     "fr_track_consensus": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_double, _I, ctypes.c_double, _P, _P, _P]),
     "fr_capture_tracks": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_double, _I, ctypes.c_double, _I, _P, _P, _P,
                                _P, _P]),
+    "fr_identity_scores": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "fr_eval_probes": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "fr_match_topk": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "fr_match_topk_host": (_I, [_P, _P, _I, _I, _P, _P]),
     "fr_embed_match": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
@@ -314,6 +316,64 @@ class Handle:
         if rc != FR_ERR_UNSUPPORTED or raise_on_clip_error:
             check(rc, self.h)
         return track_id, quality, slot, info
+
+    AGGREGATIONS = {"max": 0, "mean": 1, "topk": 2}
+
+    def identity_scores(self, Q: torch.Tensor, E: torch.Tensor, offsets, aggregation: str = "mean", k: int = 3,
+                        return_sim: bool = False):
+        """The evaluation notebook's identity scores: probes ``Q`` f32 [n,512] against a multi-embedding
+        gallery ``E`` f32 [G,512] on the device, identity i owning rows [offsets[i], offsets[i+1]) ->
+        ``out`` f32 [n, n_ids] = the max, mean or top-k mean (``aggregation`` "max" / "mean" / "topk",
+        ``k`` <= 16) of the probe's ``cosine_similarity`` against that identity's rows.  With
+        ``return_sim`` also the f32 [n,G] similarity matrix: ``(out, sim)``.  The handle's own gallery
+        is not touched."""
+        import numpy as np
+        if aggregation not in self.AGGREGATIONS:
+            raise ValueError(f"aggregation must be one of {sorted(self.AGGREGATIONS)}")
+        for name, x in (("Q", Q), ("E", E)):
+            if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 512:
+                raise ValueError(f"expected {name} as a float32 [rows,512] tensor")
+            if x.device != self.device:
+                raise ValueError(f"{name} is on {x.device}, the handle on {self.device} (no CPU fallback)")
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        n_ids = off.shape[0] - 1
+        if n_ids < 1 or int(off[-1]) != E.shape[0]:
+            raise ValueError(f"offsets must name at least one identity and end at the {E.shape[0]} rows of E")
+        Q, E = Q.contiguous(), E.contiguous()
+        n, G = Q.shape[0], E.shape[0]
+        out = torch.empty((n, n_ids), dtype=torch.float32, device=self.device)
+        sim = torch.empty((n, G), dtype=torch.float32, device=self.device) if return_sim else None
+        check(self._lib.fr_identity_scores(self.h, ptr(Q), n, ptr(E), off.ctypes.data, n_ids,
+                                           self.AGGREGATIONS[aggregation], int(k), ptr(out), ptr(sim),
+                                           stream_of(self.device)), self.h)
+        return (out, sim) if return_sim else out
+
+    def eval_probes(self, scores: torch.Tensor, true_id: torch.Tensor, thresholds):
+        """Per-probe records and threshold counts of a device score matrix ``scores`` f32 [n, n_ids]
+        with the probes' true identity indices ``true_id`` int32 [n] (outside [0, n_ids): not
+        enrolled) and up to 256 float64 ``thresholds`` -> (rec_i int32 [n,4] = predicted, best, rank,
+        has_impostor; rec_f f32 [n,4] = best score, genuine, impostor, 0; counts int64 [T,4] = tp, fp,
+        fn, genuine >= threshold) on the device (include/frhip.h: fr_eval_probes)."""
+        import numpy as np
+        if scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[1] < 1:
+            raise ValueError("expected scores as a float32 [n, n_ids] tensor with n_ids >= 1")
+        if true_id.dtype != torch.int32 or tuple(true_id.shape) != (scores.shape[0],):
+            raise ValueError("expected true_id as an int32 [n] tensor")
+        for name, x in (("scores", scores), ("true_id", true_id)):
+            if x.device != self.device:
+                raise ValueError(f"{name} is on {x.device}, the handle on {self.device} (no CPU fallback)")
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        if thr.shape[0] > 256:
+            raise ValueError("at most 256 thresholds per call")
+        scores, true_id = scores.contiguous(), true_id.contiguous()
+        n, T = scores.shape[0], thr.shape[0]
+        rec_i = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        rec_f = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        counts = torch.empty((T, 4), dtype=torch.int64, device=self.device)
+        check(self._lib.fr_eval_probes(self.h, ptr(scores), n, scores.shape[1], ptr(true_id),
+                                       thr.ctypes.data if T else None, T, ptr(rec_i), ptr(rec_f),
+                                       ptr(counts) if T else None, stream_of(self.device)), self.h)
+        return rec_i, rec_f, counts
 
     # -- alignment / quality ----------------------------------------------
     def align_faces(self, frame: torch.Tensor, landmarks, out_size: int, out: torch.Tensor):

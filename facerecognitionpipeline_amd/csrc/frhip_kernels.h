@@ -290,6 +290,30 @@ hipError_t launch_capture_tracks(const int* bbox, const double* metrics, const u
                                  long long q_limit, int target_frames, double min_quality_score, int save_partial,
                                  int* track_id, double* quality, int* slot, int* clip_info, hipStream_t s);
 
+// Model evaluation (evaluate.hip: the notebook's cosine_similarity / aggregate_* / identify_probe /
+// compute_rank_metrics and the threshold loops of evaluate_*_comprehensive).
+constexpr int EVAL_MAX_ROWS = 1024;      // gallery rows of one identity
+constexpr int EVAL_MAX_K = 16;           // top-k mean
+constexpr int EVAL_MAX_THRESHOLDS = 256;
+constexpr int EVAL_TILE_ROWS = 4096;     // gallery rows one workgroup stages in LDS
+constexpr int EVAL_TILE_IDS = 1024;      // identities one workgroup owns
+enum EvalAgg : int { AGG_MAX = 0, AGG_MEAN = 1, AGG_TOPK = 2 };
+// norm[r] = (float)sqrt(double sum of squares) of n rows of x [n][512]; *any_off |= 1 when a row has
+// |norm - 1| >= 0.01 (any_off may be NULL).
+hipError_t launch_row_norms(const float* x, int n, float* norm, int* any_off, hipStream_t s);
+// out[p][i] = aggregation of sim[p][offsets[i] .. offsets[i+1]) for n probes, after the 0.01 rule is
+// applied to every sim element (written back when write_sim).  offsets: device [n_ids + 1];
+// tiles: device [n_tiles + 1] first identities of runs of <= EVAL_TILE_IDS identities and
+// <= EVAL_TILE_ROWS rows (fr_identity_scores builds them); qnorm [n], enorm [G], e_any_off as launch_row_norms
+// wrote them.  sim [n][G] with n * G * 4 < 2 GiB.
+hipError_t launch_identity_agg(float* sim, int n, int G, const int* offsets, int n_ids, const int* tiles, int n_tiles,
+                               const float* qnorm, const float* enorm, const int* e_any_off, int aggregation, int k,
+                               bool write_sim, float* out, hipStream_t s);
+// Records and threshold counts of n probes over scores [n][n_ids] (frhip.h: fr_eval_probes); thr:
+// device [n_thr] doubles; counts must be zero at launch.
+hipError_t launch_eval_probes(const float* scores, int n, int n_ids, const int* true_id, const double* thr, int n_thr,
+                              int* rec_i, float* rec_f, long long* counts, hipStream_t s);
+
 // ---- SCRFD detector glue (detect.hip)
 constexpr int DET_MAX_CANDIDATES = 4096;  // per frame, above det_thresh, before NMS
 

@@ -26,6 +26,8 @@ long long capture_q_limit(double max_distance) {
   return q;
 }
 
+int g_eval_chunk = 0;
+
 }  // namespace frhip_rt
 
 extern "C" {
@@ -386,6 +388,120 @@ int fr_capture_tracks(fr_handle* h, const int32_t* bbox, const double* metrics, 
                            ? ": more than " + std::to_string(CAPTURE_MAX_TRACKS) + " tracks alive at once"
                            : ": a box coordinate beyond +-" + std::to_string(CAPTURE_COORD_MAX)));
   }
+  return FR_OK;
+}
+
+int fr_identity_scores(fr_handle* h, const float* Q, int n, const float* E, const int32_t* id_offsets, int n_ids,
+                       int aggregation, int k, float* out, float* sim, void* stream) {
+  // the argument checks need no handle and come first: they report the same way for h == NULL
+  std::unique_lock<std::mutex> lk;
+  if (h) lk = std::unique_lock<std::mutex>(h->mu);
+  if (n < 0 || n_ids < 1 || !id_offsets || !E || (n > 0 && (!Q || !out)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or n_ids, or NULL buffer");
+  if (aggregation < FR_AGG_MAX || aggregation > FR_AGG_TOPK)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "aggregation must be FR_AGG_MAX, _MEAN or _TOPK");
+  if (aggregation == FR_AGG_TOPK && k < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "k must be >= 1");
+  if (aggregation == FR_AGG_TOPK && k > EVAL_MAX_K)
+    return fail(h, FR_ERR_UNSUPPORTED, "top-k aggregation takes k <= " + std::to_string(EVAL_MAX_K));
+  if (id_offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "id_offsets[0] must be 0");
+  for (int i = 0; i < n_ids; ++i) {
+    const long long rows = (long long)id_offsets[i + 1] - id_offsets[i];
+    if (rows < 1 || rows > EVAL_MAX_ROWS)
+      return fail(h, FR_ERR_INVALID_ARGUMENT,
+                  "every identity needs 1.." + std::to_string(EVAL_MAX_ROWS) + " gallery rows (identity " +
+                      std::to_string(i) + " has " + std::to_string(rows) + ")");
+  }
+  const int G = id_offsets[n_ids];
+  if ((long long)G * 4 > (1ll << 31) - 1) return fail(h, FR_ERR_UNSUPPORTED, "one probe's score row must stay below 2 GiB");
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  if (n == 0) return FR_OK;
+  if (int rc = check_dev_err(h)) return rc;  // reported by earlier asynchronous work
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  // tiles of the aggregation kernel: runs of identities of <= EVAL_TILE_IDS identities and
+  // <= EVAL_TILE_ROWS rows, staged behind the offsets
+  std::vector<int32_t> stage(id_offsets, id_offsets + n_ids + 1);
+  int n_tiles = 0;
+  for (int i = 0, first = 0; i <= n_ids; ++i) {
+    if (i == n_ids || i - first == EVAL_TILE_IDS || id_offsets[i + 1] - id_offsets[first] > EVAL_TILE_ROWS) {
+      stage.push_back(first);
+      ++n_tiles;
+      first = i;
+    }
+  }
+  stage.push_back(n_ids);
+  const size_t ob = stage.size() * sizeof(int32_t);
+  int rc = ensure_buf(h, &h->tpl_offsets, &h->tpl_offsets_cap, ob);
+  if (rc) return rc;
+  FR_HIP(h, hipMemcpyAsync(h->tpl_offsets, stage.data(), ob, hipMemcpyHostToDevice, s));
+  const int* d_off = (const int*)h->tpl_offsets;
+  const int* d_tiles = d_off + n_ids + 1;
+  // row norms: [flag][n probes][G gallery rows]
+  rc = ensure_buf(h, &h->eval_ws, &h->eval_ws_cap, (1 + (size_t)n + (size_t)G) * sizeof(float));
+  if (rc) return rc;
+  int* d_flag = (int*)h->eval_ws;
+  float* d_qnorm = (float*)h->eval_ws + 1;
+  float* d_enorm = d_qnorm + n;
+  LaneWs& L = h->lane_ws[0];
+  if (ensure_stream_k(h->device, &h->cus, &L.sk_ws, &L.sk_ws_floats, &L.sk_cnt, &L.sk_cnt_cap) != FR_OK)
+    return fail(h, FR_ERR_HIP, "stream-K workspace allocation failed");
+  FR_HIP(h, hipMemsetAsync(d_flag, 0, sizeof(int), s));
+  {
+    ProfScope ps(h, s, 0.0, 0);
+    hipError_t e = launch_row_norms(Q, n, d_qnorm, nullptr, s);
+    if (e == hipSuccess) e = launch_row_norms(E, G, d_enorm, d_flag, s);
+    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("row norms launch: ") + hipGetErrorString(e));
+  }
+  ConvW g;
+  g.w = const_cast<float*>(E);
+  g.geometry(512, G, 1, 1, 1, 0);
+  // score matrices below 2 GiB (the conv epilogue's 32-bit offsets): probes in chunks
+  int nc = (int)std::max<long long>(1, std::min<long long>(n, ((1ll << 31) - 1) / ((long long)G * 4)));
+  if (g_eval_chunk > 0) nc = std::min(nc, g_eval_chunk);
+  if (!sim) {
+    rc = ensure_buf(h, (void**)&h->scores, &h->scores_cap, (size_t)nc * G * sizeof(float));
+    if (rc) return rc;
+  }
+  for (int q0 = 0; q0 < n; q0 += nc) {
+    const int qn = std::min(nc, n - q0);
+    float* chunk = sim ? sim + (size_t)q0 * G : h->scores;
+    // raw dots: no renormalisation of either side (the notebook's np.dot)
+    rc = run_conv(h, g, ConvCall{Q + (size_t)q0 * 512, chunk, qn, 1, 1, EPI_RAW}, L, s);
+    if (rc) return rc;
+    ProfScope ps(h, s, 0.0, 0);
+    hipError_t e = launch_identity_agg(chunk, qn, G, d_off, n_ids, d_tiles, n_tiles, d_qnorm + q0, d_enorm, d_flag,
+                                       aggregation, k, sim != nullptr, out + (size_t)q0 * n_ids, s);
+    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("identity scores launch: ") + hipGetErrorString(e));
+  }
+  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
+  return check_dev_err(h);
+}
+
+int fr_eval_probes(fr_handle* h, const float* scores, int n, int n_ids, const int32_t* true_id,
+                   const double* thresholds, int n_thr, int32_t* rec_i, float* rec_f, int64_t* counts, void* stream) {
+  // the argument checks need no handle and come first: they report the same way for h == NULL
+  std::unique_lock<std::mutex> lk;
+  if (h) lk = std::unique_lock<std::mutex>(h->mu);
+  if (n < 0 || n_ids < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "n must be >= 0 and n_ids >= 1");
+  if (n_thr < 0 || n_thr > EVAL_MAX_THRESHOLDS)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "n_thr must be in [0, " + std::to_string(EVAL_MAX_THRESHOLDS) + "]");
+  if ((n > 0 && (!scores || !true_id || !rec_i || !rec_f)) || (n_thr > 0 && (!thresholds || !counts)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer");
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_thr > 0) FR_HIP(h, hipMemsetAsync(counts, 0, (size_t)n_thr * 4 * sizeof(int64_t), s));
+  if (n > 0) {
+    int rc = ensure_buf(h, &h->eval_ws, &h->eval_ws_cap, EVAL_MAX_THRESHOLDS * sizeof(double));
+    if (rc) return rc;
+    if (n_thr > 0)
+      FR_HIP(h, hipMemcpyAsync(h->eval_ws, thresholds, (size_t)n_thr * sizeof(double), hipMemcpyHostToDevice, s));
+    ProfScope ps(h, s, 0.0, 0);
+    hipError_t e = launch_eval_probes(scores, n, n_ids, true_id, (const double*)h->eval_ws, n_thr, rec_i, rec_f,
+                                      (long long*)counts, s);
+    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("eval probes launch: ") + hipGetErrorString(e));
+  }
+  FR_HIP(h, hipStreamSynchronize(s));  // the thresholds were staged from pageable host memory
   return FR_OK;
 }
 

@@ -143,6 +143,11 @@ int frt_conv2d_s2band(const float* x, const float* w, float* y, int B, int H, in
   if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_s2band: ") + hipGetErrorString(e));
   return FR_OK;
 }
+int frt_set_eval_chunk(int probes) {
+  if (probes < 0) return FR_ERR_INVALID_ARGUMENT;
+  g_eval_chunk = probes;
+  return FR_OK;
+}
 int frt_set_s2_band(int on) {
   g_knobs.s2band = on != 0;
   return FR_OK;

@@ -181,6 +181,10 @@ struct fr_handle {
   // CSR offsets of fr_build_templates / fr_track_consensus / fr_capture_tracks (all synchronise)
   void* tpl_offsets = nullptr;
   size_t tpl_offsets_cap = 0;
+  // fr_identity_scores: row norms of the probes and the gallery + the off-unit flag;
+  // fr_eval_probes: the staged thresholds
+  void* eval_ws = nullptr;
+  size_t eval_ws_cap = 0;
 
   // alignment / quality workspace
   void* align_m = nullptr;  // [n][6] inverse affine maps (double)
@@ -293,6 +297,7 @@ struct fr_handle {
     (void)hipFree(match_io);
     (void)hipFree(gallery_tmp);
     (void)hipFree(tpl_offsets);
+    (void)hipFree(eval_ws);
     (void)hipFree(align_m);
     (void)hipFree(blur_out);
     (void)hipFree(blur_ws);
@@ -365,6 +370,8 @@ int finalize_model(fr_handle* h);
 // in double (q = 4 x a squared centroid distance), so that q < q_limit is the reference's
 // `distance < max_distance`; 0 for max_distance <= 0 or NaN
 long long capture_q_limit(double max_distance);
+// frt_set_eval_chunk: probes per GEMM chunk of fr_identity_scores, 0 = the 2 GiB rule
+extern int g_eval_chunk;
 
 // conv_dispatch.cpp
 // The geometry and K-step fields of conv cw over a B x H x W input in nsplit K-slices: what the

@@ -14,6 +14,8 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
     rec_i, rec_d = torch.ops.frhip.track_consensus(idx, score, offsets, 0.55, 3, 0.5)  # [T,8] i32 / [T,2] f64
     tid, quality, slot, info = torch.ops.frhip.capture_tracks(bbox, metrics, valid, frame_offsets, clip_offsets,
                                                               30, 80.0, 12, 0.5, False)  # [N] x 3, [C,4] i32
+    scores = torch.ops.frhip.identity_scores(q, gallery_rows, id_offsets, "mean", 3)   # [N, n_ids] f32
+    rec_i, rec_f, counts = torch.ops.frhip.eval_probes(scores, true_id, thresholds)    # [N,4] x 2, [T,4] i64
 
 Each op has a fake (meta) implementation, so the ops trace under
 ``torch.fx`` / ``torch.export`` with the right output shapes.
@@ -61,7 +63,7 @@ _utility: Dict[torch.device, "_lib.Handle"] = {}
 
 def utility_handle(device) -> "_lib.Handle":
     """A model-less handle on ``device`` for the entry points that need no weights
-    (``augment_faces``, ``track_consensus``, ``capture_tracks``): one per device, created on first use."""
+    (``augment_faces``, ``track_consensus``, ``capture_tracks``, ``identity_scores``, ``eval_probes``): one per device, created on first use."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
@@ -177,3 +179,31 @@ def _(bbox, metrics, valid, frame_offsets, clip_offsets, max_disappeared, max_di
     n, c = bbox.shape[0], max(len(clip_offsets) - 1, 0)
     return (bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((n,), dtype=torch.float64),
             bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((c, 4), dtype=torch.int32))
+
+
+@torch.library.custom_op("frhip::identity_scores", mutates_args=())
+def identity_scores(q: torch.Tensor, gallery: torch.Tensor, offsets: List[int], aggregation: str,
+                    k: int) -> torch.Tensor:
+    if q.device.type != "cuda":
+        raise ValueError(f"q is on {q.device}: identity_scores runs on a HIP device (no CPU fallback)")
+    return utility_handle(q.device).identity_scores(q, gallery, offsets, aggregation, k)
+
+
+@identity_scores.register_fake
+def _(q, gallery, offsets, aggregation, k):
+    return q.new_empty((q.shape[0], max(len(offsets) - 1, 0)), dtype=torch.float32)
+
+
+@torch.library.custom_op("frhip::eval_probes", mutates_args=())
+def eval_probes(scores: torch.Tensor, true_id: torch.Tensor,
+                thresholds: List[float]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    if scores.device.type != "cuda":
+        raise ValueError(f"scores are on {scores.device}: eval_probes runs on a HIP device (no CPU fallback)")
+    return utility_handle(scores.device).eval_probes(scores, true_id, thresholds)
+
+
+@eval_probes.register_fake
+def _(scores, true_id, thresholds):
+    n = scores.shape[0]
+    return (scores.new_empty((n, 4), dtype=torch.int32), scores.new_empty((n, 4), dtype=torch.float32),
+            scores.new_empty((len(thresholds), 4), dtype=torch.int64))

@@ -234,6 +234,60 @@ int fr_capture_tracks(fr_handle* h,
                       int32_t* slot,     /* device [total] */
                       int32_t* clip_info /* device [n_clips][4] */, void* stream);
 
+/* Model evaluation, step 1 (evaluate_models_v2.ipynb: cosine_similarity, aggregate_max / _mean /
+ * _topk as identify_probe applies them): the score of every probe against every identity of a
+ * multi-embedding gallery.  Q: device [n][512]; E: device [G][512], an explicit matrix (the handle's
+ * serving gallery is neither read nor changed); identity i owns rows [id_offsets[i], id_offsets[i+1])
+ * of E (host offsets, id_offsets[0] = 0, 1..FR_EVAL_MAX_ROWS rows each, G = id_offsets[n_ids]).
+ *   sim[p][r]   cosine_similarity(Q[p], E[r]): the f32 dot when |norm - 1| < 0.01 for both rows, else
+ *               dot / (norm_q * norm_e) in f32.  A row's norm is the f32 rounding of the square root of
+ *               its double sum of squares, computed once per call.  The dots run on the implicit-GEMM
+ *               conv path without renormalisation, in the handle's precision mode (fr_set_precision).
+ *   out[p][i]   FR_AGG_MAX: the f32 maximum of the identity's sim values.  FR_AGG_MEAN: the f32
+ *               rounding of (double sum in row order) / count.  FR_AGG_TOPK: the min(k, count) largest
+ *               values summed in double in descending order, divided by their number, rounded to f32
+ *               (k is ignored by the other two).
+ * out[p] depends on nothing but sim[p] and the offsets.  sim: device [n][G] and then filled, or NULL
+ * (the scores then live in the handle's workspace, a chunk of probes below 2 GiB at a time).  Any
+ * handle will do, finalised or not.  Synchronises (the offsets are staged from the host).  n == 0 is
+ * a no-op.  NULL buffers, n < 0, n_ids < 1, id_offsets[0] != 0, an empty identity or one over
+ * FR_EVAL_MAX_ROWS, an unknown aggregation and FR_AGG_TOPK with k < 1 -> FR_ERR_INVALID_ARGUMENT;
+ * FR_AGG_TOPK with k > FR_EVAL_MAX_K -> FR_ERR_UNSUPPORTED (all checked before the handle, so also
+ * reported for h == NULL). */
+#define FR_AGG_MAX 0
+#define FR_AGG_MEAN 1
+#define FR_AGG_TOPK 2
+#define FR_EVAL_MAX_ROWS 1024 /* gallery rows of one identity */
+#define FR_EVAL_MAX_K 16
+int fr_identity_scores(fr_handle* h, const float* Q /* device [n][512] */, int n,
+                       const float* E /* device [G][512] */, const int32_t* id_offsets /* host [n_ids + 1] */,
+                       int n_ids, int aggregation, int k, float* out /* device [n][n_ids] */,
+                       float* sim /* device [n][G], or NULL */, void* stream);
+
+/* Model evaluation, step 2: the per-probe part of identify_probe(threshold=0.0) and
+ * compute_rank_metrics plus the threshold loops of the evaluate_*_comprehensive functions, in one
+ * launch over a score matrix that is on the device.  Probe p has row a = scores[p] and t = true_id[p];
+ * a t outside [0, n_ids) means "not enrolled" and reads nothing.
+ *   best        the largest score, equal scores to the lowest identity index (Python's stable
+ *               sorted(..., reverse=True) over the dict order)
+ *   predicted   best, or -1 if a[best] < 0 (identify_probe returns None)
+ *   enrolled    rank = 1 + #{j : a[j] > a[t]} + #{j < t : a[j] == a[t]}; genuine = a[t];
+ *               impostor = max over j != t, has_impostor = (n_ids > 1)
+ *   otherwise   rank = 0; genuine = 0.0f; impostor = a[best], has_impostor = 1
+ * rec_i[p] = {predicted, best, rank, has_impostor}; rec_f[p] = {a[best], genuine, impostor or -1.0f, 0}.
+ * counts[j] for thresholds[j], with accepted = (double)a[best] >= thresholds[j] (in double: the
+ * notebook's thresholds are float64): {tp: accepted, enrolled and predicted == t; fp: accepted and
+ * not tp; fn: not accepted; the number of enrolled probes with (double)genuine >= thresholds[j]}.
+ * The call zeroes counts itself.  Deterministic: integer sums; a record depends on nothing but its
+ * row.  Scores must not be NaN.  Any handle will do.  Synchronises (the thresholds are staged from the
+ * host).  n == 0 zeroes counts only.  NULL buffers, n < 0, n_ids < 1 and n_thr outside
+ * [0, FR_EVAL_MAX_THRESHOLDS] -> FR_ERR_INVALID_ARGUMENT (checked before the handle). */
+#define FR_EVAL_MAX_THRESHOLDS 256
+int fr_eval_probes(fr_handle* h, const float* scores /* device [n][n_ids] */, int n, int n_ids,
+                   const int32_t* true_id /* device [n] */, const double* thresholds /* host [n_thr] */, int n_thr,
+                   int32_t* rec_i /* device [n][4] */, float* rec_f /* device [n][4] */,
+                   int64_t* counts /* device [n_thr][4] */, void* stream);
+
 /* FaceAligner.align for n faces of one frame (face_recognition.py:50-75): similarity fit of
  * each face's 5 landmarks to the reference template (cv2.estimateAffinePartial2D semantics,
  * host, double) then warpAffine INTER_LINEAR / BORDER_CONSTANT 0 on the device, so the crops

@@ -122,6 +122,11 @@ int frt_maxpool3(const float* x, int B, int H, int W, int C, float* y, void* str
 /* Row-wise top-k of a [n][G] score matrix (score desc, equal scores by descending index; k in [1, G]). */
 int frt_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, void* stream);
 
+/* Process-wide: fr_identity_scores scores at most `probes` probes per GEMM chunk (0: the built-in
+ * rule, the most whose [probes][G] score matrix stays below 2 GiB), so a test can put a chunk seam
+ * inside a small batch. */
+int frt_set_eval_chunk(int probes);
+
 /* Detector internals of fr_detect for n <= max_frames frames: letterbox + network only.
  * heads: device f32, the three levels' maps back to back, each [n][H/s][W/s][32] for
  * s = 8, 16, 32 (channels: cls a0, cls a1 logits | bbox a0 (4), a1 (4) | kps a0 (10), a1 (10)

@@ -83,7 +83,21 @@ stored to pin them.
   ``compute_quality_score`` and saved ``frame_NNN`` number of every detection and the
   ``metadata.json`` numbers of every saved track.  scipy (``cdist``) is the installed one.
 
-Usage: ``python tools/make_golden.py [embed] [c3] [resize] [backups] [refpkl] [gate] [image] [track] [capture] [dropin]``
+* ``evaluate.npz`` — the evaluation functions of ``evaluate_models_v2.ipynb`` (``cosine_similarity``,
+  ``compute_all_similarities``, ``aggregate_*``, ``identify_probe``, ``compute_rank_metrics``,
+  ``compute_dprime``, ``bootstrap_confidence_interval`` and the four ``evaluate_*_comprehensive``).  The
+  notebook is read as JSON at run time and only the code cells that define those functions are
+  executed (``tqdm`` is the identity; pandas and sklearn are the installed ones); none of its text is
+  written anywhere.  They run on the cases of ``tests/_eval_cases.py`` (``exact``: basis-vector
+  galleries and hand-built score lists; ``seeded``: 13 identities of 1..1024 rows, segments and
+  negatives; ``norms``: off-unit rows): per case and (aggregation, k) the reference's similarity and
+  identity-score matrices, predictions, ranks, every threshold table, the per-identity table and the
+  verification figures, as arrays; the inputs are pinned by SHA-256.  The builder asserts the
+  margins of ``_eval_cases.check_margins`` on the reference's numbers, that the host statements of
+  ``facerecognitionpipeline_amd.evaluate_models`` reproduce the reference bit for bit on ``exact``,
+  and that ``eval_probes_host`` reproduces its records and counts on every recorded score matrix.
+
+Usage: ``python tools/make_golden.py [embed] [c3] [resize] [backups] [refpkl] [gate] [image] [track] [capture] [evaluate] [dropin]``
 (no argument: all).
 """
 from __future__ import annotations
@@ -202,7 +216,7 @@ def main() -> None:
     if not os.path.isdir(REF):
         raise SystemExit("reference not present; golden files are generated in the build container only")
     parts = set(sys.argv[1:]) or {"embed", "c3", "resize", "backups", "refpkl", "gate", "image", "track",
-                                     "capture", "dropin"}
+                                     "capture", "evaluate", "dropin"}
     os.makedirs(OUT, exist_ok=True)
     tmp = tempfile.mkdtemp(prefix="frgolden_")
     with open(os.path.join(tmp, "cv2.py"), "w") as f:
@@ -599,6 +613,155 @@ def main() -> None:
         assert reached >= CC.REQUIRED, sorted(CC.REQUIRED - reached)
         np.savez_compressed(os.path.join(OUT, "capture_tracks.npz"), **out)
         print("capture", len(built), "sessions;", os.path.getsize(os.path.join(OUT, "capture_tracks.npz")), "bytes")
+
+    if "evaluate" in parts:
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        import _eval_cases as EC
+        from facerecognitionpipeline_amd import evaluate_models as EM
+        wanted = ("cosine_similarity", "compute_all_similarities", "aggregate_max", "aggregate_mean", "aggregate_topk",
+                  "identify_probe", "compute_rank_metrics", "compute_dprime", "bootstrap_confidence_interval",
+                  "evaluate_probes_comprehensive", "evaluate_verification_comprehensive",
+                  "evaluate_impostors_comprehensive", "evaluate_segmented_comprehensive")
+        ns = {}
+        exec("import numpy as np\nimport pandas as pd\nfrom typing import Dict, List, Tuple, Optional\n"
+             "from sklearn.metrics import roc_curve, auc\ndef tqdm(it, **kw):\n    return it\n", ns)
+        with open(os.path.join(REF, "evaluate_models_v2.ipynb")) as f:
+            nb = json.load(f)
+        for cell in nb["cells"]:  # the cells that define the functions, and nothing else of the notebook
+            src = "".join(cell["source"])
+            if cell["cell_type"] == "code" and any(f"def {n}(" in src for n in wanted):
+                exec(compile(src, "evaluate_models_v2.ipynb", "exec"), ns)
+        assert all(n in ns for n in wanted)
+        f32 = np.float32
+
+        def table(df, cols):
+            assert list(df.columns) == list(cols), list(df.columns)
+            return df[list(cols)].to_numpy(np.float64)
+
+        def ver_arrays(ver, pre, out):
+            out[pre + "ver_table"] = table(ver["threshold_results"], EC.VER_COLUMNS)
+            out[pre + "ver_equal"] = np.array([ver[k] for k in EC.VER_EQUAL], np.float64)
+            out[pre + "ver_float"] = np.array([ver[k] for k in EC.VER_FLOAT], np.float64)
+            out[pre + "ver_genuine"] = np.array(ver["genuine_scores"], f32)
+            out[pre + "ver_impostor"] = np.array(ver["impostor_scores"], f32)
+            out[pre + "ver_auc_full"] = np.float64(EM.roc_curve_auc(ver["genuine_scores"], ver["impostor_scores"])[2])
+            assert out[pre + "ver_auc_full"] == ver["roc_auc"], (pre, out[pre + "ver_auc_full"], ver["roc_auc"])
+
+        out = {"labels": np.array([c["label"] for c in EC.all_cases()])}
+        buckets = set()
+        for case in EC.all_cases():
+            label, gallery = case["label"], case["gallery"]
+            gnames = list(gallery)
+            thr = EC.thresholds_of(case)
+            names, Q = EC.pack(case["positive"]["all"])
+            nnames, NQ = EC.pack(case["negative"])
+            _gn, E = EC.pack(gallery)
+            offsets = EC.offsets_of(gallery)
+            tid = EC.true_ids(names, gallery)
+            exact = label.startswith("exact")
+            out[f"{label}__sha256"] = np.array(EC.case_sha(case))
+            out[f"{label}__thresholds"] = thr
+            sim = np.array([[s for _n, s in ns["compute_all_similarities"](q, gallery)] for q in Q], f32)
+            nsim = np.array([[s for _n, s in ns["compute_all_similarities"](q, gallery)] for q in NQ], f32)
+            out[f"{label}__sim"], out[f"{label}__neg_sim"] = sim, nsim
+            h_sim = EM.similarity_matrix_host(Q, E)
+            if exact:
+                assert h_sim.tobytes() == sim.tobytes(), label
+            else:
+                assert np.abs(h_sim - sim).max() <= EC.SCORE_TOL, (label, np.abs(h_sim - sim).max())
+            for agg, k in case["runs"]:
+                pre = f"{label}__{agg}{k}__"
+                with quiet():
+                    res = ns["evaluate_probes_comprehensive"](gallery, case["positive"], list(thr), aggregation=agg, k=k)
+                    ver = ns["evaluate_verification_comprehensive"](gallery, case["positive"], case["negative"],
+                                                                    list(thr), aggregation=agg, k=k)
+                    imp = ns["evaluate_impostors_comprehensive"](gallery, case["negative"], list(thr),
+                                                                 aggregation=agg, k=k)
+                    nscores = np.array([[ns["identify_probe"](q, gallery, 0.0, agg, k)[2][g] for g in gnames]
+                                        for q in NQ], f32)
+                preds = res["all_predictions"]
+                assert [p["true_identity"] for p in preds] == names
+                scores = np.array([[p["identity_scores"][g] for g in gnames] for p in preds], f32)
+                for p in preds:
+                    assert all(type(v) is np.float32 for v in p["identity_scores"].values())
+                rec_i = np.zeros((len(preds), 4), np.int32)
+                rec_f = np.zeros((len(preds), 4), f32)
+                for r, p in enumerate(preds):
+                    ranked = sorted(p["identity_scores"].items(), key=lambda kv: kv[1], reverse=True)
+                    rr = p["rank_metrics"]["reciprocal_rank"]
+                    rank = int(round(1.0 / rr)) if rr > 0 else 0
+                    assert (rank > 0) == (p["true_identity"] in gallery)
+                    assert [p["rank_metrics"][f"rank{c}"] for c in (1, 5, 10)] == [1 <= rank <= c for c in (1, 5, 10)]
+                    assert p["score"] == ranked[0][1]
+                    others = [v for g, v in p["identity_scores"].items() if g != p["true_identity"]]
+                    rec_i[r] = (gnames.index(p["predicted_identity"]) if p["predicted_identity"] is not None else -1,
+                                gnames.index(ranked[0][0]), rank, 1 if others else 0)
+                    rec_f[r] = (p["score"], p["identity_scores"].get(p["true_identity"], 0),
+                                max(others) if others else -1.0, 0.0)
+                    buckets.add((label.split("_")[0], 0 if rank == 0 else 1 if rank == 1 else 5 if rank <= 5 else
+                                 10 if rank <= 10 else 11))
+                tab = table(res["threshold_results"], EC.PROBE_COLUMNS)
+                vtab = table(ver["threshold_results"], EC.VER_COLUMNS)
+                counts = np.stack([tab[:, 11], tab[:, 12], tab[:, 13], vtab[:, 4]], axis=1).astype(np.int64)
+                assert np.array_equal(counts, np.stack([tab[:, 11], tab[:, 12], tab[:, 13], vtab[:, 4]], axis=1))
+                # the host statements are the reference, or the fixture is not written
+                h_i, h_f, h_c = EM.eval_probes_host(scores, tid, thr)
+                assert np.array_equal(h_i, rec_i) and h_f.tobytes() == rec_f.tobytes() and np.array_equal(h_c, counts), pre
+                n_i, n_f, n_c = EM.eval_probes_host(nscores, np.full(len(nscores), -1, np.int32), thr)
+                assert n_f[:, 0].tobytes() == np.array(imp["impostor_scores"], f32).tobytes(), pre
+                assert np.array_equal(n_c[:, 2], table(imp["threshold_results"], EC.IMP_COLUMNS)[:, 3]), pre
+                assert np.array_equal(n_c[:, 2], vtab[:, 6]), pre
+                h_scores = EM.identity_scores_host(h_sim, offsets, agg, k)
+                if exact:
+                    assert h_scores.tobytes() == scores.tobytes(), pre
+                else:
+                    assert np.abs(h_scores - scores).max() <= EC.SCORE_TOL, (pre, np.abs(h_scores - scores).max())
+                    EC.check_margins(scores, tid, nscores, thr, EC.float64_scores(Q, E, offsets, agg, k),
+                                     EC.float64_scores(NQ, E, offsets, agg, k))
+                out[pre + "scores"], out[pre + "neg_scores"] = scores, nscores
+                out[pre + "rec_i"], out[pre + "rec_f"], out[pre + "counts"] = rec_i, rec_f, counts
+                out[pre + "probe_table"] = tab
+                pid = res["per_identity"]
+                out[pre + "pid_names"] = np.array(list(pid))
+                out[pre + "pid_table"] = np.array([[v["rank1"], v["rank5"], v["rank10"], v["mrr"], v["n_samples"]]
+                                                   for v in pid.values()], np.float64)
+                out[pre + "pid_genuine"] = np.array([s for v in pid.values() for s in v["genuine_scores"]], f32)
+                out[pre + "pid_impostor_sum"] = np.array([np.sum(np.array(v["impostor_scores"], np.float64))
+                                                          for v in pid.values()], np.float64)
+                ver_arrays(ver, pre, out)
+                out[pre + "imp_table"] = table(imp["threshold_results"], EC.IMP_COLUMNS)
+                out[pre + "imp_stats"] = np.array([imp["mean_impostor_score"], imp["std_impostor_score"]], np.float64)
+                out[pre + "dprime_fn"] = np.float64(ns["compute_dprime"](ver["genuine_scores"], ver["impostor_scores"]))
+                segments = [s for s in case["positive"] if s != "all"]
+                if segments:
+                    with quiet():
+                        seg = ns["evaluate_segmented_comprehensive"](gallery, case["positive"], case["negative"],
+                                                                     list(thr), aggregation=agg, k=k)
+                    assert list(seg) == segments
+                    for sname, sres in seg.items():
+                        out[pre + f"seg_{sname}__probe_table"] = table(sres["identification"]["threshold_results"],
+                                                                       EC.PROBE_COLUMNS)
+                        out[pre + f"seg_{sname}__predicted"] = np.array(
+                            [gnames.index(p["predicted_identity"]) if p["predicted_identity"] is not None else -1
+                             for p in sres["identification"]["all_predictions"]], np.int32)
+                        ver_arrays(sres["verification"], pre + f"seg_{sname}__", out)
+                print("evaluate", pre, "probes", len(preds), "rank1", tab[0, 1], "auc", ver["roc_auc"], "eer", ver["eer"])
+            for k in case.get("topk_only", ()):
+                with quiet():
+                    sc = np.array([[ns["identify_probe"](q, gallery, 0.0, "topk", k)[2][g] for g in gnames] for q in Q], f32)
+                assert np.abs(EM.identity_scores_host(h_sim, offsets, "topk", k) - sc).max() <= EC.SCORE_TOL
+                out[f"{label}__topk{k}__scores_only"] = sc
+        assert {b for lab, b in buckets if lab == "seeded"} == {0, 1, 5, 10, 11}, sorted(buckets)
+        # bootstrap_confidence_interval: the reference draws from numpy's global generator; with the same
+        # generator state the mirror draws the same samples
+        data = [float(x) for x in np.linspace(0.1, 0.9, 23)]
+        np.random.seed(1234)
+        ci_ref = ns["bootstrap_confidence_interval"](data, n_bootstrap=200)
+        np.random.seed(1234)
+        assert EM.bootstrap_confidence_interval(data, n_bootstrap=200) == ci_ref
+        out["bootstrap_data"], out["bootstrap_ci_seed1234_n200"] = np.array(data), np.array(ci_ref, np.float64)
+        np.savez_compressed(os.path.join(OUT, "evaluate.npz"), **out)
+        print("evaluate", len(out), "arrays;", os.path.getsize(os.path.join(OUT, "evaluate.npz")), "bytes")
 
     if "dropin" in parts:
         import shutil
