@@ -118,6 +118,17 @@ def stream_of(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _csr_offsets(offsets, end=None, message="", min_slices=0):
+    """CSR offsets as a contiguous int32 vector and its slice count; ``ValueError(message)`` for fewer
+    than ``min_slices`` slices or, with ``end``, slices that do not end at it."""
+    import numpy as np
+    off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+    n = off.shape[0] - 1
+    if end is not None and (n < min_slices or (n > 0 and int(off[-1]) != end)):
+        raise ValueError(message)
+    return off, n
+
+
 class Handle:
     """Owns one ``fr_handle``: a model (after ``load_state_dict``) and/or a gallery."""
 
@@ -135,6 +146,13 @@ class Handle:
         self.gallery_tag = None  # (owner, version) of the rows in HBM; see GalleryManager._sync_device
         check(self._lib.fr_create(architecture.encode(), model_type.encode(), idx, int(max_batch), ctypes.byref(h)))
         self.h = h
+
+    def _require_device(self, name: str, *tensors) -> None:
+        """``name`` names the tensors, e.g. "idx / score"."""
+        if any(x.device != self.device for x in tensors):
+            raise ValueError(f"{name} {'is' if len(tensors) == 1 else 'are'} on "
+                             f"{' / '.join(str(x.device) for x in tensors)}, the handle on {self.device} "
+                             "(no CPU fallback)")
 
     def close(self) -> None:
         if getattr(self, "h", None) and self._lib is not None:
@@ -224,11 +242,9 @@ class Handle:
     def build_templates(self, emb: torch.Tensor, offsets, method: str = "mean", min_similarity: float = 0.70):
         """Templates of len(offsets)-1 students whose samples are CSR rows of ``emb`` [total,512]
         -> (templates f32 [S,512], kept int32 [S]) on the device."""
-        import numpy as np
         methods = {"mean": 0, "median": 1, "weighted_mean": 2}
         m = methods.get(method, 0)  # the reference falls back to mean for unknown methods
-        off = np.ascontiguousarray(offsets, dtype=np.int32)
-        S = off.shape[0] - 1
+        off, S = _csr_offsets(offsets)
         emb = emb.to(device=self.device, dtype=torch.float32).contiguous()
         tpl = torch.empty((max(S, 0), 512), dtype=torch.float32, device=self.device)
         kept = torch.empty((max(S, 0),), dtype=torch.int32, device=self.device)
@@ -251,17 +267,11 @@ class Handle:
         for len(offsets)-1 tracks whose frames are CSR rows of the device top-k output ``idx`` int32 /
         ``score`` float32 [total,k] -> (int32 [T,8] = status, winner row, winner count, pool size,
         second count, frames, quality frames, 0; float64 [T,2] = confidence, ratio) on the device."""
-        import numpy as np
         if (idx.dim() != 2 or idx.dtype != torch.int32 or score.dtype != torch.float32
                 or tuple(score.shape) != tuple(idx.shape)):
             raise ValueError("expected idx int32 [total,k] and score float32 [total,k]")
-        if idx.device != self.device or score.device != self.device:
-            raise ValueError(f"idx / score are on {idx.device} / {score.device}, the handle on {self.device} "
-                             "(no CPU fallback)")
-        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
-        T = off.shape[0] - 1
-        if T < 0 or (T > 0 and int(off[-1]) != idx.shape[0]):
-            raise ValueError(f"offsets must end at the {idx.shape[0]} rows of idx / score")
+        self._require_device("idx / score", idx, score)
+        off, T = _csr_offsets(offsets, idx.shape[0], f"offsets must end at the {idx.shape[0]} rows of idx / score")
         idx, score = idx.contiguous(), score.contiguous()
         out_i = torch.empty((T, 8), dtype=torch.int32, device=self.device)
         out_d = torch.empty((T, 2), dtype=torch.float64, device=self.device)
@@ -283,7 +293,6 @@ class Handle:
         tracks completed, frames saved, error) on the device.  A clip past the kernel's limits raises
         NotImplementedError; with ``raise_on_clip_error=False`` the outputs are returned instead and
         ``clip_info[:, 3]`` names the clips (their track_id is 0 and slot -1 throughout)."""
-        import numpy as np
         if valid.dtype == torch.bool:
             valid = valid.to(torch.uint8)
         if (bbox.dim() != 2 or bbox.shape[1] != 4 or bbox.dtype != torch.int32 or metrics.dtype != torch.float64
@@ -291,17 +300,13 @@ class Handle:
                 or tuple(valid.shape) != (bbox.shape[0],)):
             raise ValueError("expected bbox int32 [total,4], metrics float64 [total,5] and valid uint8 [total]")
         for name, x in (("bbox", bbox), ("metrics", metrics), ("valid", valid)):
-            if x.device != self.device:
-                raise ValueError(f"{name} is on {x.device}, the handle on {self.device} (no CPU fallback)")
-        fo = np.ascontiguousarray(frame_offsets, dtype=np.int32).reshape(-1)
-        if fo.shape[0] < 1:
+            self._require_device(name, x)
+        fo, F = _csr_offsets(frame_offsets)
+        if F < 0:
             raise ValueError("frame_offsets needs at least its leading 0")
-        co = np.ascontiguousarray([0, fo.shape[0] - 1] if clip_offsets is None else clip_offsets,
-                                  dtype=np.int32).reshape(-1)
-        C = co.shape[0] - 1
-        if C < 0 or (C > 0 and int(co[-1]) != fo.shape[0] - 1):
-            raise ValueError(f"clip_offsets must end at the {fo.shape[0] - 1} frames of frame_offsets")
-        if int(fo[-1]) != bbox.shape[0]:
+        co, C = _csr_offsets([0, F] if clip_offsets is None else clip_offsets, F,
+                             f"clip_offsets must end at the {F} frames of frame_offsets")
+        if int(fo[-1]) != bbox.shape[0]:  # also without frames
             raise ValueError(f"frame_offsets must end at the {bbox.shape[0]} rows of bbox / metrics / valid")
         bbox, metrics, valid = bbox.contiguous(), metrics.contiguous(), valid.contiguous()
         total = bbox.shape[0]
@@ -327,18 +332,14 @@ class Handle:
         ``k`` <= 16) of the probe's ``cosine_similarity`` against that identity's rows.  With
         ``return_sim`` also the f32 [n,G] similarity matrix: ``(out, sim)``.  The handle's own gallery
         is not touched."""
-        import numpy as np
         if aggregation not in self.AGGREGATIONS:
             raise ValueError(f"aggregation must be one of {sorted(self.AGGREGATIONS)}")
         for name, x in (("Q", Q), ("E", E)):
             if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 512:
                 raise ValueError(f"expected {name} as a float32 [rows,512] tensor")
-            if x.device != self.device:
-                raise ValueError(f"{name} is on {x.device}, the handle on {self.device} (no CPU fallback)")
-        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
-        n_ids = off.shape[0] - 1
-        if n_ids < 1 or int(off[-1]) != E.shape[0]:
-            raise ValueError(f"offsets must name at least one identity and end at the {E.shape[0]} rows of E")
+            self._require_device(name, x)
+        off, n_ids = _csr_offsets(offsets, E.shape[0], "offsets must name at least one identity and end at the "
+                                  f"{E.shape[0]} rows of E", min_slices=1)
         Q, E = Q.contiguous(), E.contiguous()
         n, G = Q.shape[0], E.shape[0]
         out = torch.empty((n, n_ids), dtype=torch.float32, device=self.device)
@@ -360,8 +361,7 @@ class Handle:
         if true_id.dtype != torch.int32 or tuple(true_id.shape) != (scores.shape[0],):
             raise ValueError("expected true_id as an int32 [n] tensor")
         for name, x in (("scores", scores), ("true_id", true_id)):
-            if x.device != self.device:
-                raise ValueError(f"{name} is on {x.device}, the handle on {self.device} (no CPU fallback)")
+            self._require_device(name, x)
         thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
         if thr.shape[0] > 256:
             raise ValueError("at most 256 thresholds per call")

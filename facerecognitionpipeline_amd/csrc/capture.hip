@@ -27,6 +27,7 @@
 // clip.  A clip that would hold more than CAPTURE_MAX_TRACKS live tracks, or has a coordinate beyond
 // +-CAPTURE_COORD_MAX, gets its error word set, track_id 0 and slot -1 throughout, and nothing is
 // written out of range.
+#include "block_reduce.h"
 #include "frhip_kernels.h"
 
 #pragma clang fp contract(off)
@@ -45,17 +46,6 @@ static_assert(CAPTURE_MAX_TRACKS + CAPTURE_MAX_FACES == CAP_BLOCK, "one thread p
 static_assert(CAP_PER_THREAD <= 32, "accepted flags of a thread's detections are one int mask");
 
 constexpr unsigned long long NO_PAIR = ~0ull;
-
-// Block sum over 4 waves of 64.  It starts with a barrier, so LDS written before the call is
-// visible after it and `red` may be reused by the next call.
-__device__ __forceinline__ int block_sum_int(int v, int* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // FrameAccumulator.compute_quality_score (face_detection.py:137-153)
 __device__ __forceinline__ double quality_score(const double* m) {
@@ -107,7 +97,7 @@ __global__ __launch_bounds__(CAP_BLOCK) void capture_tracks_kernel(
     qual[i] = q;
     state[i] = valid[at] != 0 && !(q < min_quality);
   }
-  int error = block_sum_int(bad, red_i) > 0 ? CAPTURE_ERR_COORD : 0;
+  int error = block_sum(bad, red_i) > 0 ? CAPTURE_ERR_COORD : 0;
 
   // ---- the tracker, frame by frame.  Its loops over the list and over the frame's detections
   // are short and wait on LDS: they are unrolled by 4 so that the reads of four entries overlap.
@@ -274,8 +264,8 @@ __global__ __launch_bounds__(CAP_BLOCK) void capture_tracks_kernel(
     slot[d0 + i] = s;
     saved += s >= 0;
   }
-  completed = block_sum_int(completed, red_i);
-  saved = block_sum_int(saved, red_i);
+  completed = block_sum(completed, red_i);
+  saved = block_sum(saved, red_i);
   if (t == 0) info[0] = next_id - 1, info[1] = completed, info[2] = saved, info[3] = 0;
 }
 

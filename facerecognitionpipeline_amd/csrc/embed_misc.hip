@@ -9,6 +9,7 @@
 //   l2norm_rows_kernel q/(||q||+1e-8) (gallery_manager.py:195).
 //   topk_kernel        argsort(S)[::-1][:k] (gallery_manager.py:197) with the
 //                      documented tie policy: score desc, then gallery row desc.
+#include "block_reduce.h"
 #include "frhip_kernels.h"
 
 #include <float.h>
@@ -165,19 +166,8 @@ hipError_t launch_stem(const uint8_t* img, int B, const float* lut, const float*
   return hipGetLastError();
 }
 
-// Block-wide sum over 256 threads (4 waves of 64).
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int wid = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[wid] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // Block-wide sum over 1024 threads whose waves 4..15 hold zeros: the same value as
-// block_sum_256 over waves 0..3 (the extra terms add exact zeros).
+// block_reduce.h's block_sum over waves 0..3 (the extra terms add exact zeros).
 __device__ __forceinline__ float block_sum_1024(float v, float* red) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -274,7 +264,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
   const float* r = q + (long long)blockIdx.x * d;
   float ss = 0.f;
   for (int c = threadIdx.x; c < d; c += 256) ss += r[c] * r[c];
-  const float nrm = sqrtf(block_sum_256(ss, red)) + 1e-8f;
+  const float nrm = sqrtf(block_sum(ss, red)) + 1e-8f;
   for (int c = threadIdx.x; c < d; c += 256) out[(long long)blockIdx.x * d + c] = r[c] / nrm;
 }
 
@@ -443,7 +433,7 @@ __global__ __launch_bounds__(256) void scores_small_kernel(const float* __restri
   const int qi = blockIdx.y;
   const float* r = q + (long long)qi * 512;
   const float r0 = r[tid], r1 = r[tid + 256];
-  const float nrm = sqrtf(block_sum_256(r0 * r0 + r1 * r1, red)) + 1e-8f;
+  const float nrm = sqrtf(block_sum(r0 * r0 + r1 * r1, red)) + 1e-8f;
   qn[tid] = r0 / nrm;
   qn[tid + 256] = r1 / nrm;
   __syncthreads();

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "block_reduce.h"
 #include "frhip_kernels.h"
 
 #pragma clang fp contract(off)
@@ -54,8 +55,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void row_norms_kernel(const float* __re
     s += (double)v.z * (double)v.z;
     s += (double)v.w * (double)v.w;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if (lane != 0) return;
   const float nrm = (float)sqrt(s);
   norm[row] = nrm;

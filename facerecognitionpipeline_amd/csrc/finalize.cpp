@@ -1,4 +1,5 @@
-// libfrhip handle state: error reporting, buffers, the state-dict schema, BatchNorm folding and
+// libfrhip handle state: error reporting, buffers, the helpers the entry points share (the lock,
+// the CSR offsets check, the offsets staging), the state-dict schema, BatchNorm folding and
 // the upload of every folded tensor, the derived filter arenas and the workspace.  What it
 // replaces in the reference:
 //   FaceEmbedder.__init__/load_state_dict   face_embedder.py:27-62
@@ -48,6 +49,49 @@ int ensure_buf(fr_handle* h, void** p, size_t* cap, size_t bytes) {
   *cap = 0;
   FR_HIP(h, hipMalloc(p, bytes));
   *cap = bytes;
+  return FR_OK;
+}
+
+int launch_fail(fr_handle* h, const char* what, hipError_t e) {
+  return fail(h, FR_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+}
+
+std::unique_lock<std::mutex> lock_handle(fr_handle* h) {
+  return h ? std::unique_lock<std::mutex>(h->mu) : std::unique_lock<std::mutex>();
+}
+
+std::string csr_check(const int32_t* offsets, int n, long long min_len, long long max_len, const CsrNouns& nouns,
+                      const int32_t* outer) {
+  const std::string array = nouns.array, item = nouns.item;
+  if (n > 0 && !outer && offsets[0] != 0) return array + "[0] must be 0";
+  for (int i = 0; i < n; ++i) {
+    const long long len =
+        outer ? (long long)offsets[outer[i + 1]] - offsets[outer[i]] : (long long)offsets[i + 1] - offsets[i];
+    if (len >= min_len && len <= max_len) continue;
+    const std::string at = item + " " + std::to_string(i);
+    return (len < 0 ? array + " decrease at " + at + ": " : std::string()) + "every " + item + " needs " +
+           std::to_string(min_len) + ".." + std::to_string(max_len) + " " + nouns.unit + " (" + at + " has " +
+           std::to_string(len) + ")";
+  }
+  return std::string();
+}
+
+int stage_int32(fr_handle* h, hipStream_t s, std::initializer_list<Int32Span> parts, const int** dev) {
+  size_t total = 0;
+  for (const Int32Span& p : parts) total += p.n;
+  if (int rc = ensure_buf(h, &h->csr_stage, &h->csr_stage_cap, total * sizeof(int32_t))) return rc;
+  const int32_t* src = parts.begin()->p;
+  if (parts.size() > 1) {  // packed on the host first: one copy per call
+    h->csr_host.clear();
+    for (const Int32Span& p : parts) h->csr_host.insert(h->csr_host.end(), p.p, p.p + p.n);
+    src = h->csr_host.data();
+  }
+  FR_HIP(h, hipMemcpyAsync(h->csr_stage, src, total * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  const int* d = (const int*)h->csr_stage;
+  for (const Int32Span& p : parts) {
+    *dev++ = d;
+    d += p.n;
+  }
   return FR_OK;
 }
 

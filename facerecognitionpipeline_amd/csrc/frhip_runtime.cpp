@@ -1,9 +1,10 @@
 // libfrhip public C API (include/frhip.h): argument checks, the handle's lock and device, and
 // calls into the runtime's other translation units (runtime.h lists them; their headers name the
-// reference code each replaces).  The gallery rows kept in HBM here replace
+// reference code each replaces): the model, gallery-row, match, align, detect, settings and
+// profiling calls.  The calls over CSR batches are in batch_ops.cpp.  The gallery rows kept in
+// HBM here replace
 //   GalleryManager.get_gallery_embeddings   gallery_manager.py:177-187 (A10)
 #include <algorithm>
-#include <cmath>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -13,22 +14,6 @@
 
 using namespace frhip;
 using namespace frhip_rt;
-
-namespace frhip_rt {
-
-long long capture_q_limit(double max_distance) {
-  if (!(max_distance > 0.0)) return 0;  // also NaN: `distances.min() < nan` is never true
-  // past every q in range (q <= 2^45: coordinates within +-FR_CAPTURE_COORD_MAX)
-  if (max_distance >= 4194304.0) return 1ll << 46;
-  long long q = (long long)std::floor(4.0 * max_distance * max_distance);
-  while (q > 0 && std::sqrt((double)(q - 1) / 4.0) >= max_distance) --q;
-  while (std::sqrt((double)q / 4.0) < max_distance) ++q;
-  return q;
-}
-
-int g_eval_chunk = 0;
-
-}  // namespace frhip_rt
 
 extern "C" {
 
@@ -151,7 +136,7 @@ int fr_augment_faces(fr_handle* h, const uint8_t* crops, int n, int height, int 
   AugTables tab;
   augment_tables(height, width, &tab);
   const hipError_t e = launch_augment(crops, n, height, width, num_augmentations, tab, out, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("augment launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_fail(h, "augment", e);
   return FR_OK;
 }
 
@@ -258,253 +243,6 @@ int fr_gallery_read(fr_handle* h, int row0, int n, float* out, int dst_is_device
   return FR_OK;
 }
 
-int fr_build_templates(fr_handle* h, const float* emb, const int32_t* offsets, int n_students, int method,
-                       float min_similarity, float* templates, int32_t* kept, void* stream) {
-  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (n_students < 0 || (n_students > 0 && (!emb || !offsets || !templates)))
-    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n_students or NULL buffer");
-  if (method < FR_TEMPLATE_MEAN || method > FR_TEMPLATE_WEIGHTED_MEAN)
-    return fail(h, FR_ERR_INVALID_ARGUMENT, "method must be FR_TEMPLATE_MEAN, _MEDIAN or _WEIGHTED_MEAN");
-  if (n_students == 0) return FR_OK;
-  if (offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
-  for (int i = 0; i < n_students; ++i) {
-    const int n = offsets[i + 1] - offsets[i];
-    if (n < 1 || n > TEMPLATE_MAX_SAMPLES)
-      return fail(h, FR_ERR_INVALID_ARGUMENT,
-                  "every student needs 1.." + std::to_string(TEMPLATE_MAX_SAMPLES) + " samples (student " +
-                      std::to_string(i) + " has " + std::to_string(n) + ")");
-  }
-  DeviceGuard dg(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t ob = (size_t)(n_students + 1) * sizeof(int32_t);
-  int rc = ensure_buf(h, &h->tpl_offsets, &h->tpl_offsets_cap, ob);
-  if (rc) return rc;
-  FR_HIP(h, hipMemcpyAsync(h->tpl_offsets, offsets, ob, hipMemcpyHostToDevice, s));
-  hipError_t e = launch_templates(emb, (const int*)h->tpl_offsets, n_students, method, min_similarity, templates,
-                                  kept, s);
-  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("template launch: ") + hipGetErrorString(e));
-  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
-  return FR_OK;
-}
-
-int fr_track_consensus(fr_handle* h, const int32_t* idx, const float* score, int k, const int32_t* offsets,
-                       int n_tracks, double min_quality, int min_frames, double similarity_threshold,
-                       int32_t* out_i, double* out_d, void* stream) {
-  // the argument checks need no handle and come first: they report the same way for h == NULL
-  std::unique_lock<std::mutex> lk;
-  if (h) lk = std::unique_lock<std::mutex>(h->mu);
-  if (n_tracks < 0 || (n_tracks > 0 && (!idx || !score || !offsets || !out_i || !out_d)))
-    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n_tracks or NULL buffer");
-  if (k < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "k must be >= 1");
-  if (min_frames < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "min_frames must be >= 1");
-  if (n_tracks > 0 && offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
-  for (int i = 0; i < n_tracks; ++i) {
-    const long long n = (long long)offsets[i + 1] - offsets[i];
-    if (n < 1 || n > TRACK_MAX_FRAMES)
-      return fail(h, FR_ERR_INVALID_ARGUMENT,
-                  "every track needs 1.." + std::to_string(TRACK_MAX_FRAMES) + " frames (track " +
-                      std::to_string(i) + " has " + std::to_string(n) + ")");
-  }
-  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
-  if (n_tracks == 0) return FR_OK;
-  DeviceGuard dg(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t ob = (size_t)(n_tracks + 1) * sizeof(int32_t);
-  int rc = ensure_buf(h, &h->tpl_offsets, &h->tpl_offsets_cap, ob);
-  if (rc) return rc;
-  FR_HIP(h, hipMemcpyAsync(h->tpl_offsets, offsets, ob, hipMemcpyHostToDevice, s));
-  hipError_t e = launch_track_consensus(idx, score, k, (const int*)h->tpl_offsets, n_tracks, min_quality, min_frames,
-                                        similarity_threshold, out_i, out_d, s);
-  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("track consensus launch: ") + hipGetErrorString(e));
-  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
-  return FR_OK;
-}
-
-int fr_capture_tracks(fr_handle* h, const int32_t* bbox, const double* metrics, const uint8_t* valid,
-                      const int32_t* frame_offsets, const int32_t* clip_offsets, int n_clips, int max_disappeared,
-                      double max_distance, int target_frames, double min_quality_score, int save_partial,
-                      int32_t* track_id, double* quality, int32_t* slot, int32_t* clip_info, void* stream) {
-  // the argument checks need no handle and come first: they report the same way for h == NULL
-  std::unique_lock<std::mutex> lk;
-  if (h) lk = std::unique_lock<std::mutex>(h->mu);
-  if (n_clips < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "n_clips must be >= 0");
-  if (target_frames < 1 || target_frames > CAPTURE_MAX_TARGET)
-    return fail(h, FR_ERR_INVALID_ARGUMENT, "target_frames must be in [1, " + std::to_string(CAPTURE_MAX_TARGET) + "]");
-  if (max_disappeared < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "max_disappeared must be >= 0");
-  int n_frames = 0, total = 0;
-  if (n_clips > 0) {
-    if (!frame_offsets || !clip_offsets) return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer (offsets)");
-    if (clip_offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "clip_offsets[0] must be 0");
-    if (frame_offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "frame_offsets[0] must be 0");
-    for (int c = 0; c < n_clips; ++c)
-      if (clip_offsets[c + 1] < clip_offsets[c])
-        return fail(h, FR_ERR_INVALID_ARGUMENT, "clip_offsets decrease at clip " + std::to_string(c));
-    n_frames = clip_offsets[n_clips];
-    for (int f = 0; f < n_frames; ++f) {
-      const long long n = (long long)frame_offsets[f + 1] - frame_offsets[f];
-      if (n < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "frame_offsets decrease at frame " + std::to_string(f));
-      if (n > CAPTURE_MAX_FACES)
-        return fail(h, FR_ERR_INVALID_ARGUMENT,
-                    "a frame holds at most " + std::to_string(CAPTURE_MAX_FACES) + " detections (frame " +
-                        std::to_string(f) + " has " + std::to_string(n) + ")");
-    }
-    for (int c = 0; c < n_clips; ++c) {
-      const long long n = (long long)frame_offsets[clip_offsets[c + 1]] - frame_offsets[clip_offsets[c]];
-      if (n > CAPTURE_MAX_DETS)
-        return fail(h, FR_ERR_INVALID_ARGUMENT,
-                    "a clip holds at most " + std::to_string(CAPTURE_MAX_DETS) + " detections (clip " +
-                        std::to_string(c) + " has " + std::to_string(n) + ")");
-    }
-    total = frame_offsets[n_frames];
-    if (!clip_info || (total > 0 && (!bbox || !metrics || !valid || !track_id || !quality || !slot)))
-      return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer");
-  }
-  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
-  if (n_clips == 0) return FR_OK;
-  DeviceGuard dg(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  // frame offsets, then clip offsets, in one staging buffer
-  std::vector<int32_t> off(frame_offsets, frame_offsets + n_frames + 1);
-  off.insert(off.end(), clip_offsets, clip_offsets + n_clips + 1);
-  const size_t ob = off.size() * sizeof(int32_t);
-  int rc = ensure_buf(h, &h->tpl_offsets, &h->tpl_offsets_cap, ob);
-  if (rc) return rc;
-  FR_HIP(h, hipMemcpyAsync(h->tpl_offsets, off.data(), ob, hipMemcpyHostToDevice, s));
-  const int* d_off = (const int*)h->tpl_offsets;
-  hipError_t e = launch_capture_tracks(bbox, metrics, valid, d_off, d_off + n_frames + 1, n_clips, max_disappeared,
-                                       capture_q_limit(max_distance), target_frames, min_quality_score,
-                                       save_partial != 0, track_id, quality, slot, clip_info, s);
-  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("capture tracks launch: ") + hipGetErrorString(e));
-  std::vector<int32_t> info((size_t)n_clips * 4);
-  FR_HIP(h, hipMemcpyAsync(info.data(), clip_info, info.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
-  for (int c = 0; c < n_clips; ++c) {
-    const int err = info[(size_t)c * 4 + 3];
-    if (err)
-      return fail(h, FR_ERR_UNSUPPORTED,
-                  "clip " + std::to_string(c) +
-                      (err == CAPTURE_ERR_TRACKS
-                           ? ": more than " + std::to_string(CAPTURE_MAX_TRACKS) + " tracks alive at once"
-                           : ": a box coordinate beyond +-" + std::to_string(CAPTURE_COORD_MAX)));
-  }
-  return FR_OK;
-}
-
-int fr_identity_scores(fr_handle* h, const float* Q, int n, const float* E, const int32_t* id_offsets, int n_ids,
-                       int aggregation, int k, float* out, float* sim, void* stream) {
-  // the argument checks need no handle and come first: they report the same way for h == NULL
-  std::unique_lock<std::mutex> lk;
-  if (h) lk = std::unique_lock<std::mutex>(h->mu);
-  if (n < 0 || n_ids < 1 || !id_offsets || !E || (n > 0 && (!Q || !out)))
-    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or n_ids, or NULL buffer");
-  if (aggregation < FR_AGG_MAX || aggregation > FR_AGG_TOPK)
-    return fail(h, FR_ERR_INVALID_ARGUMENT, "aggregation must be FR_AGG_MAX, _MEAN or _TOPK");
-  if (aggregation == FR_AGG_TOPK && k < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "k must be >= 1");
-  if (aggregation == FR_AGG_TOPK && k > EVAL_MAX_K)
-    return fail(h, FR_ERR_UNSUPPORTED, "top-k aggregation takes k <= " + std::to_string(EVAL_MAX_K));
-  if (id_offsets[0] != 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "id_offsets[0] must be 0");
-  for (int i = 0; i < n_ids; ++i) {
-    const long long rows = (long long)id_offsets[i + 1] - id_offsets[i];
-    if (rows < 1 || rows > EVAL_MAX_ROWS)
-      return fail(h, FR_ERR_INVALID_ARGUMENT,
-                  "every identity needs 1.." + std::to_string(EVAL_MAX_ROWS) + " gallery rows (identity " +
-                      std::to_string(i) + " has " + std::to_string(rows) + ")");
-  }
-  const int G = id_offsets[n_ids];
-  if ((long long)G * 4 > (1ll << 31) - 1) return fail(h, FR_ERR_UNSUPPORTED, "one probe's score row must stay below 2 GiB");
-  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
-  if (n == 0) return FR_OK;
-  if (int rc = check_dev_err(h)) return rc;  // reported by earlier asynchronous work
-  DeviceGuard dg(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  // tiles of the aggregation kernel: runs of identities of <= EVAL_TILE_IDS identities and
-  // <= EVAL_TILE_ROWS rows, staged behind the offsets
-  std::vector<int32_t> stage(id_offsets, id_offsets + n_ids + 1);
-  int n_tiles = 0;
-  for (int i = 0, first = 0; i <= n_ids; ++i) {
-    if (i == n_ids || i - first == EVAL_TILE_IDS || id_offsets[i + 1] - id_offsets[first] > EVAL_TILE_ROWS) {
-      stage.push_back(first);
-      ++n_tiles;
-      first = i;
-    }
-  }
-  stage.push_back(n_ids);
-  const size_t ob = stage.size() * sizeof(int32_t);
-  int rc = ensure_buf(h, &h->tpl_offsets, &h->tpl_offsets_cap, ob);
-  if (rc) return rc;
-  FR_HIP(h, hipMemcpyAsync(h->tpl_offsets, stage.data(), ob, hipMemcpyHostToDevice, s));
-  const int* d_off = (const int*)h->tpl_offsets;
-  const int* d_tiles = d_off + n_ids + 1;
-  // row norms: [flag][n probes][G gallery rows]
-  rc = ensure_buf(h, &h->eval_ws, &h->eval_ws_cap, (1 + (size_t)n + (size_t)G) * sizeof(float));
-  if (rc) return rc;
-  int* d_flag = (int*)h->eval_ws;
-  float* d_qnorm = (float*)h->eval_ws + 1;
-  float* d_enorm = d_qnorm + n;
-  LaneWs& L = h->lane_ws[0];
-  if (ensure_stream_k(h->device, &h->cus, &L.sk_ws, &L.sk_ws_floats, &L.sk_cnt, &L.sk_cnt_cap) != FR_OK)
-    return fail(h, FR_ERR_HIP, "stream-K workspace allocation failed");
-  FR_HIP(h, hipMemsetAsync(d_flag, 0, sizeof(int), s));
-  {
-    ProfScope ps(h, s, 0.0, 0);
-    hipError_t e = launch_row_norms(Q, n, d_qnorm, nullptr, s);
-    if (e == hipSuccess) e = launch_row_norms(E, G, d_enorm, d_flag, s);
-    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("row norms launch: ") + hipGetErrorString(e));
-  }
-  ConvW g;
-  g.w = const_cast<float*>(E);
-  g.geometry(512, G, 1, 1, 1, 0);
-  // score matrices below 2 GiB (the conv epilogue's 32-bit offsets): probes in chunks
-  int nc = (int)std::max<long long>(1, std::min<long long>(n, ((1ll << 31) - 1) / ((long long)G * 4)));
-  if (g_eval_chunk > 0) nc = std::min(nc, g_eval_chunk);
-  if (!sim) {
-    rc = ensure_buf(h, (void**)&h->scores, &h->scores_cap, (size_t)nc * G * sizeof(float));
-    if (rc) return rc;
-  }
-  for (int q0 = 0; q0 < n; q0 += nc) {
-    const int qn = std::min(nc, n - q0);
-    float* chunk = sim ? sim + (size_t)q0 * G : h->scores;
-    // raw dots: no renormalisation of either side (the notebook's np.dot)
-    rc = run_conv(h, g, ConvCall{Q + (size_t)q0 * 512, chunk, qn, 1, 1, EPI_RAW}, L, s);
-    if (rc) return rc;
-    ProfScope ps(h, s, 0.0, 0);
-    hipError_t e = launch_identity_agg(chunk, qn, G, d_off, n_ids, d_tiles, n_tiles, d_qnorm + q0, d_enorm, d_flag,
-                                       aggregation, k, sim != nullptr, out + (size_t)q0 * n_ids, s);
-    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("identity scores launch: ") + hipGetErrorString(e));
-  }
-  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
-  return check_dev_err(h);
-}
-
-int fr_eval_probes(fr_handle* h, const float* scores, int n, int n_ids, const int32_t* true_id,
-                   const double* thresholds, int n_thr, int32_t* rec_i, float* rec_f, int64_t* counts, void* stream) {
-  // the argument checks need no handle and come first: they report the same way for h == NULL
-  std::unique_lock<std::mutex> lk;
-  if (h) lk = std::unique_lock<std::mutex>(h->mu);
-  if (n < 0 || n_ids < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "n must be >= 0 and n_ids >= 1");
-  if (n_thr < 0 || n_thr > EVAL_MAX_THRESHOLDS)
-    return fail(h, FR_ERR_INVALID_ARGUMENT, "n_thr must be in [0, " + std::to_string(EVAL_MAX_THRESHOLDS) + "]");
-  if ((n > 0 && (!scores || !true_id || !rec_i || !rec_f)) || (n_thr > 0 && (!thresholds || !counts)))
-    return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer");
-  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
-  DeviceGuard dg(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  if (n_thr > 0) FR_HIP(h, hipMemsetAsync(counts, 0, (size_t)n_thr * 4 * sizeof(int64_t), s));
-  if (n > 0) {
-    int rc = ensure_buf(h, &h->eval_ws, &h->eval_ws_cap, EVAL_MAX_THRESHOLDS * sizeof(double));
-    if (rc) return rc;
-    if (n_thr > 0)
-      FR_HIP(h, hipMemcpyAsync(h->eval_ws, thresholds, (size_t)n_thr * sizeof(double), hipMemcpyHostToDevice, s));
-    ProfScope ps(h, s, 0.0, 0);
-    hipError_t e = launch_eval_probes(scores, n, n_ids, true_id, (const double*)h->eval_ws, n_thr, rec_i, rec_f,
-                                      (long long*)counts, s);
-    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("eval probes launch: ") + hipGetErrorString(e));
-  }
-  FR_HIP(h, hipStreamSynchronize(s));  // the thresholds were staged from pageable host memory
-  return FR_OK;
-}
-
 int fr_gallery_size(fr_handle* h, int* G) {
   if (!h || !G) return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL argument");
   std::lock_guard<std::mutex> lk(h->mu);
@@ -606,14 +344,14 @@ int fr_warp_affine(fr_handle* h, const uint8_t* frame, int height, int width, co
   hipStream_t s = (hipStream_t)stream;
   if (n <= WARP_MAPS_BY_VALUE) {  // maps in the kernel arguments: no copy, no sync
     const hipError_t e = launch_warp_affine_by_value(frame, height, width, minv.data(), n, out_size, out, s);
-    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("warp launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return launch_fail(h, "warp", e);
     return FR_OK;
   }
   int rc = ensure_buf(h, &h->align_m, &h->align_m_cap, minv.size() * sizeof(double));
   if (rc) return rc;
   FR_HIP(h, hipMemcpyAsync(h->align_m, minv.data(), minv.size() * sizeof(double), hipMemcpyHostToDevice, s));
   hipError_t e = launch_warp_affine(frame, height, width, (const double*)h->align_m, n, out_size, out, s);
-  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("warp launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_fail(h, "warp", e);
   FR_HIP(h, hipStreamSynchronize(s));
   return FR_OK;
 }
@@ -638,7 +376,7 @@ int fr_blur_scores(fr_handle* h, const uint8_t* crops, int n, int height, int wi
     const int m = std::min(per, n - off);
     hipError_t e = launch_blur(crops + (size_t)off * img, m, height, width, channels, (double*)h->blur_out + off,
                                h->blur_ws, s);
-    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("blur launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return launch_fail(h, "blur", e);
   }
   FR_HIP(h, hipMemcpyAsync(scores, h->blur_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
   FR_HIP(h, hipStreamSynchronize(s));

@@ -17,6 +17,7 @@
 // row-sequential axis-0 sums, correctly rounded div/sqrt); the Gram dot products
 // are f32 wave reductions, so avg_i agrees with numpy's BLAS to ~1e-7, not bit
 // for bit (a threshold decision could differ only within that of 0.70).
+#include "block_reduce.h"
 #include "frhip_kernels.h"
 
 #pragma clang fp contract(off)
@@ -29,20 +30,8 @@ namespace {
 __device__ __forceinline__ float wave_dot(const float (&ei)[8], const float* __restrict__ ej, int lane) {
   const float4 a = *reinterpret_cast<const float4*>(ej + lane * 8);
   const float4 b = *reinterpret_cast<const float4*>(ej + lane * 8 + 4);
-  float d = ei[0] * a.x + ei[1] * a.y + ei[2] * a.z + ei[3] * a.w + ei[4] * b.x + ei[5] * b.y + ei[6] * b.z +
-            ei[7] * b.w;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
-  return d;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
+  return wave_sum(ei[0] * a.x + ei[1] * a.y + ei[2] * a.z + ei[3] * a.w + ei[4] * b.x + ei[5] * b.y + ei[6] * b.z +
+                  ei[7] * b.w);
 }
 
 }  // namespace

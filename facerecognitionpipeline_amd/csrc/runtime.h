@@ -1,7 +1,11 @@
 // Internals shared by the libfrhip runtime translation units: the handle, folded-parameter types
 // and the launch helpers.
-//   frhip_runtime.cpp  the public fr_* C API (include/frhip.h)
-//   finalize.cpp       handle helpers, state-dict schema, BatchNorm folding, arenas, workspace
+//   frhip_runtime.cpp  the public fr_* C API (include/frhip.h): model, gallery rows, match, align,
+//                      detect, settings, profiling
+//   batch_ops.cpp      the fr_* calls over CSR batches: templates, track consensus, capture
+//                      sessions, identity scores, probe evaluation
+//   finalize.cpp       handle and entry-point helpers, state-dict schema, BatchNorm folding, arenas,
+//                      workspace
 //   conv_dispatch.cpp  run_conv and its kernel-selection rules
 //   embed_forward.cpp  lanes, the layout plan, the IR forward, graphs, resize, gallery match
 //   align_host.cpp     cv2.estimateAffinePartial2D and the augmentation tables (host only)
@@ -11,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -178,9 +183,11 @@ struct fr_handle {
   size_t match_io_cap = 0;
   void* gallery_tmp = nullptr;  // tail staging for row deletes
   size_t gallery_tmp_cap = 0;
-  // CSR offsets of fr_build_templates / fr_track_consensus / fr_capture_tracks (all synchronise)
-  void* tpl_offsets = nullptr;
-  size_t tpl_offsets_cap = 0;
+  // int32 arrays the batch calls stage from the host (stage_int32): the CSR offsets of students,
+  // tracks, frames and clips, and fr_identity_scores' offsets and tile list (all synchronise)
+  void* csr_stage = nullptr;
+  size_t csr_stage_cap = 0;
+  std::vector<int32_t> csr_host;  // the packed host copy of a call that stages several arrays
   // fr_identity_scores: row norms of the probes and the gallery + the off-unit flag;
   // fr_eval_probes: the staged thresholds
   void* eval_ws = nullptr;
@@ -296,7 +303,7 @@ struct fr_handle {
     (void)hipFree(scores);
     (void)hipFree(match_io);
     (void)hipFree(gallery_tmp);
-    (void)hipFree(tpl_offsets);
+    (void)hipFree(csr_stage);
     (void)hipFree(eval_ws);
     (void)hipFree(align_m);
     (void)hipFree(blur_out);
@@ -320,6 +327,32 @@ int check_dev_err(fr_handle* h);
     if (e_ != hipSuccess)                                                                        \
       return ::frhip_rt::fail(h, FR_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
   } while (0)
+
+// "<what> launch: <HIP's text>" as the handle's error; returns FR_ERR_HIP.
+int launch_fail(fr_handle* h, const char* what, hipError_t e);
+// The handle's lock, or no lock for h == NULL: for the calls that check their arguments before the
+// handle, so that those checks report the same way without one.
+std::unique_lock<std::mutex> lock_handle(fr_handle* h);
+
+// The nouns of csr_check's messages, e.g. {"offsets", "track", "frames"}.
+struct CsrNouns {
+  const char *array, *item, *unit;
+};
+// Checks the CSR array offsets[0 .. n]: offsets[0] == 0 and every slice length in [min_len, max_len],
+// in long long, so decreasing or wrapping offsets are reported.  With `outer` (itself checked CSR
+// offsets into `offsets`) slice i runs from offsets[outer[i]] to offsets[outer[i + 1]].  Returns
+// the error text, or an empty string.
+std::string csr_check(const int32_t* offsets, int n, long long min_len, long long max_len, const CsrNouns& nouns,
+                      const int32_t* outer = nullptr);
+
+// Copies host int32 arrays back to back into h->csr_stage with one copy on stream s; dev[i] is the
+// device address of parts[i].  The host memory is pageable: the caller synchronises s before it
+// returns.
+struct Int32Span {
+  const int32_t* p;
+  size_t n;
+};
+int stage_int32(fr_handle* h, hipStream_t s, std::initializer_list<Int32Span> parts, const int** dev);
 
 // Restores the caller's current device on scope exit.
 struct DeviceGuard {
@@ -365,7 +398,7 @@ int ensure_winograd(fr_handle* h);
 // fr_finalize under the handle's lock and device: fold, upload, allocate the workspace
 int finalize_model(fr_handle* h);
 
-// frhip_runtime.cpp
+// batch_ops.cpp
 // fr_capture_tracks' match threshold: the smallest integer q >= 0 with sqrt(q / 4.0) >= max_distance
 // in double (q = 4 x a squared centroid distance), so that q < q_limit is the reference's
 // `distance < max_distance`; 0 for max_distance <= 0 or NaN

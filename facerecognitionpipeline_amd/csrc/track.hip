@@ -17,10 +17,11 @@
 //
 // Everything past the f32 score loads is integer or double arithmetic.  The counts and the ranking
 // are integer reductions; the confidence sum runs in one fixed order (per thread in frame order,
-// then a fixed shuffle tree, then the four waves in order), so a track's record depends on
-// nothing but its own frames.  Where the pool is the quality frames of the default min_quality
-// (f32 scores in [0.55, 2): multiples of 2^-24) every partial sum of <= 1024 of them is exact in
-// double, so that fixed order gives what any order gives.
+// then block_reduce.h's block_sum_double: a fixed shuffle tree, then the four waves in order), so a
+// track's record depends on nothing but its own frames.  Where the pool is the quality frames of
+// the default min_quality (f32 scores in [0.55, 2): multiples of 2^-24) every partial sum of
+// <= 1024 of them is exact in double, so that fixed order gives what any order gives.
+#include "block_reduce.h"
 #include "frhip_kernels.h"
 
 #pragma clang fp contract(off)
@@ -32,35 +33,6 @@ namespace {
 constexpr int TRACK_BLOCK = 256;
 constexpr int TRACK_PER_THREAD = TRACK_MAX_FRAMES / TRACK_BLOCK;
 static_assert(TRACK_MAX_FRAMES == 1024, "vote keys pack the first frame in 10 bits");
-
-// Block reductions over 4 waves of 64.  Each starts with a barrier, so LDS written before the call
-// is visible after it and `red` may be reused by the next call.
-__device__ __forceinline__ int block_sum_int(int v, int* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__device__ __forceinline__ int block_max_int(int v, int* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return max(max(red[0], red[1]), max(red[2], red[3]));
-}
-
-__device__ __forceinline__ double block_sum_double(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 }  // namespace
 
@@ -85,7 +57,7 @@ __global__ __launch_bounds__(TRACK_BLOCK) void track_consensus_kernel(
     sc[i] = s;
     nq_mine += (double)s >= min_quality;
   }
-  const int nq = block_sum_int(nq_mine, red_i);
+  const int nq = block_sum(nq_mine, red_i);
   const bool all = nq == 0;  // no quality frame: the pool is every frame
   const int pool = all ? N : nq;
   for (int i = t; i < N; i += TRACK_BLOCK) in_pool[i] = all || (double)sc[i] >= min_quality;
@@ -111,12 +83,12 @@ __global__ __launch_bounds__(TRACK_BLOCK) void track_consensus_kernel(
     }
     kmax = max(kmax, key[m]);
   }
-  const int wkey = block_max_int(kmax, red_i);  // > 0: the pool is never empty
+  const int wkey = block_max(kmax, red_i);  // > 0: the pool is never empty
   int kmax2 = 0;
 #pragma unroll
   for (int m = 0; m < TRACK_PER_THREAD; ++m)
     if (key[m] != wkey) kmax2 = max(kmax2, key[m]);
-  const int skey = block_max_int(kmax2, red_i);
+  const int skey = block_max(kmax2, red_i);
   const int winner_count = wkey >> 10, second_count = skey >> 10;
   const int winner_row = rows[TRACK_MAX_FRAMES - 1 - (wkey & (TRACK_MAX_FRAMES - 1))];
   // ---- confidence: the winner's pool scores, summed in double in a fixed order

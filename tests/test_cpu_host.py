@@ -90,6 +90,37 @@ def test_gallery_records_and_templates(tmp_path, golden_dir):
     assert np.allclose(gm3.get_gallery_embeddings()[0], gm.get_gallery_embeddings()[0])
 
 
+def test_build_templates_argument_errors_without_gpu():
+    """fr_build_templates checks its arguments before the handle, like the other CSR batch calls, so
+    a NULL handle still gets a text that names the bad argument."""
+    import ctypes
+    from facerecognitionpipeline_amd import _lib
+    lib = _lib.load()
+    emb = (ctypes.c_float * (8 * 512))()
+    tpl = (ctypes.c_float * (2 * 512))()
+    kept = (ctypes.c_int32 * 2)()
+    max_samples = 1024  # frhip.h: 1..1024 rows per student
+
+    def call(emb=emb, offsets=(0, 3, 8), n_students=2, method=0, tpl=tpl):
+        off = (ctypes.c_int32 * len(offsets))(*offsets) if offsets is not None else None
+        rc = lib.fr_build_templates(None, emb, off, n_students, method, 0.7, tpl, kept, None)
+        return rc, lib.fr_last_error(None)
+
+    for kw, text in (({}, b"NULL handle"), ({"n_students": 0, "offsets": None}, b"NULL handle"),
+                     ({"emb": None}, b"NULL buffer"), ({"offsets": None}, b"NULL buffer"),
+                     ({"tpl": None}, b"NULL buffer"), ({"n_students": -1}, b"n_students"),
+                     ({"method": 3}, b"method"), ({"method": -1}, b"method"),
+                     ({"offsets": (1, 3), "n_students": 1}, b"offsets[0]"),
+                     ({"offsets": (0, 0, 2)}, b"student 0 has 0"),           # empty student
+                     ({"offsets": (0, 3, 2)}, b"student 1 has -1"),          # decreasing offsets
+                     ({"offsets": (0, max_samples + 1), "n_students": 1}, b"student 0 has 1025"),
+                     ({"offsets": (0, 1, -2**31)}, b"student 1 has -2147483649")):   # lengths do not wrap
+        rc, msg = call(**kw)
+        assert rc == _lib.FR_ERR_INVALID_ARGUMENT, kw
+        assert text in msg, (kw, msg)
+    assert not any(tpl) and not any(kept)  # nothing was written
+
+
 def test_reference_backup_json_loads(tmp_path, golden_dir):
     """A reference export_for_backup JSON reproduces the fixture templates."""
     import json
