@@ -9,7 +9,7 @@ fallback.
 from .arch import block_specs, flop_per_face, state_dict_schema  # noqa: F401
 
 __all__ = ["FaceEmbedder", "GalleryManager", "FaceMatcher", "StudentEnrollment", "SimpleTracker", "FrameAccumulator",
-           "CameraFaceCapture", "block_specs", "flop_per_face", "state_dict_schema"]
+           "CameraFaceCapture", "LiveRecognitionTracker", "LiveFaceRecognition", "block_specs", "flop_per_face", "state_dict_schema"]
 
 
 def __getattr__(name):
@@ -28,4 +28,7 @@ def __getattr__(name):
     if name in ("SimpleTracker", "FrameAccumulator", "CameraFaceCapture"):
         from . import face_detection
         return getattr(face_detection, name)
+    if name in ("LiveRecognitionTracker", "LiveFaceRecognition"):
+        from . import face_recognition_live
+        return getattr(face_recognition_live, name)
     raise AttributeError(name)

@@ -45,6 +45,7 @@ _SIGNATURES = {
     "fr_track_consensus": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_double, _I, ctypes.c_double, _P, _P, _P]),
     "fr_capture_tracks": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_double, _I, ctypes.c_double, _I, _P, _P, _P,
                                _P, _P]),
+    "fr_live_tracks": (_I, [_P, _P, _P, _P, _P, _I, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "fr_identity_scores": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "fr_eval_probes": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "fr_match_topk": (_I, [_P, _P, _I, _I, _P, _P, _P]),
@@ -321,6 +322,44 @@ class Handle:
         if rc != FR_ERR_UNSUPPORTED or raise_on_clip_error:
             check(rc, self.h)
         return track_id, quality, slot, info
+
+    def live_tracks(self, bbox: torch.Tensor, metrics: torch.Tensor, frame_offsets, clip_offsets=None,
+                    max_distance: float = 100, recognition_interval: int = 30, max_attempts: int = 3,
+                    buffer_size: int = 10, raise_on_clip_error: bool = True):
+        """The reference's ``LiveFaceRecognition._simple_track_assignment`` and the gating and frame
+        selection of ``LiveRecognitionTracker`` (face_recognition_live.py:18-80, :249-285) for
+        len(clip_offsets)-1 live sessions in one launch.  ``bbox`` int32 [total,4] and ``metrics``
+        float64 [total,2] (det_score, blur_score) on the device; frames and clips as
+        :meth:`capture_tracks` takes them -> (track_id int32 [total] from 0, prev int32 [total],
+        attempt int32 [total], best int32 [total], clip_info int32 [C,4] = tracks opened, candidates,
+        frames, error) on the device; ``prev`` and ``best`` are global detection indices, -1 for none.
+        A clip past the coordinate limit raises NotImplementedError; with
+        ``raise_on_clip_error=False`` the outputs are returned instead and ``clip_info[:, 3]`` names
+        the clips (their track_id is 0 and the rest -1 throughout)."""
+        if (bbox.dim() != 2 or bbox.shape[1] != 4 or bbox.dtype != torch.int32 or metrics.dtype != torch.float64
+                or tuple(metrics.shape) != (bbox.shape[0], 2)):
+            raise ValueError("expected bbox int32 [total,4] and metrics float64 [total,2]")
+        for name, x in (("bbox", bbox), ("metrics", metrics)):
+            self._require_device(name, x)
+        fo, F = _csr_offsets(frame_offsets)
+        if F < 0:
+            raise ValueError("frame_offsets needs at least its leading 0")
+        co, C = _csr_offsets([0, F] if clip_offsets is None else clip_offsets, F,
+                             f"clip_offsets must end at the {F} frames of frame_offsets")
+        if int(fo[-1]) != bbox.shape[0]:  # also without frames
+            raise ValueError(f"frame_offsets must end at the {bbox.shape[0]} rows of bbox / metrics")
+        bbox, metrics = bbox.contiguous(), metrics.contiguous()
+        total = bbox.shape[0]
+        track_id, prev, attempt, best = (torch.empty((total,), dtype=torch.int32, device=self.device)
+                                         for _ in range(4))
+        info = torch.empty((max(C, 0), 4), dtype=torch.int32, device=self.device)
+        rc = self._lib.fr_live_tracks(self.h, ptr(bbox), ptr(metrics), fo.ctypes.data, co.ctypes.data, C,
+                                      float(max_distance), int(recognition_interval), int(max_attempts),
+                                      int(buffer_size), ptr(track_id), ptr(prev), ptr(attempt), ptr(best), ptr(info),
+                                      stream_of(self.device))
+        if rc != FR_ERR_UNSUPPORTED or raise_on_clip_error:
+            check(rc, self.h)
+        return track_id, prev, attempt, best, info
 
     AGGREGATIONS = {"max": 0, "mean": 1, "topk": 2}
 

@@ -1,8 +1,8 @@
 // libfrhip public C API (include/frhip.h), the calls over CSR batches: fr_build_templates,
-// fr_track_consensus, fr_capture_tracks, fr_identity_scores and fr_eval_probes.  They share one
-// shape: lock_handle; the argument checks, which need no handle and so report the same way for
-// h == NULL (csr_check for the offsets); "NULL handle"; the offsets staged with stage_int32; the
-// launch; one stream synchronise, because the staging read pageable host memory.
+// fr_track_consensus, fr_capture_tracks, fr_live_tracks, fr_identity_scores and fr_eval_probes.
+// They share one shape: lock_handle; the argument checks, which need no handle and so report the
+// same way for h == NULL (csr_check for the offsets); "NULL handle"; the offsets staged with
+// stage_int32; the launch; one stream synchronise, because the staging read pageable host memory.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -125,6 +125,53 @@ int fr_capture_tracks(fr_handle* h, const int32_t* bbox, const double* metrics, 
                            ? ": more than " + std::to_string(CAPTURE_MAX_TRACKS) + " tracks alive at once"
                            : ": a box coordinate beyond +-" + std::to_string(CAPTURE_COORD_MAX)));
   }
+  return FR_OK;
+}
+
+int fr_live_tracks(fr_handle* h, const int32_t* bbox, const double* metrics, const int32_t* frame_offsets,
+                   const int32_t* clip_offsets, int n_clips, double max_distance, int recognition_interval,
+                   int max_attempts, int buffer_size, int32_t* track_id, int32_t* prev, int32_t* attempt,
+                   int32_t* best, int32_t* clip_info, void* stream) {
+  auto lk = lock_handle(h);
+  if (n_clips < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "n_clips must be >= 0");
+  if (recognition_interval < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "recognition_interval must be >= 1");
+  if (max_attempts < 1 || max_attempts > LIVE_MAX_ATTEMPTS)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "max_attempts must be in [1, " + std::to_string(LIVE_MAX_ATTEMPTS) + "]");
+  if (buffer_size < 1 || buffer_size > LIVE_MAX_BUFFER)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "buffer_size must be in [1, " + std::to_string(LIVE_MAX_BUFFER) + "]");
+  int n_frames = 0;
+  if (n_clips > 0) {
+    if (!frame_offsets || !clip_offsets) return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer (offsets)");
+    // clips of any number of frames and detections; frames may be empty; a cap per frame
+    std::string bad = csr_check(clip_offsets, n_clips, 0, INT32_MAX, {"clip_offsets", "clip", "frames"});
+    n_frames = bad.empty() ? clip_offsets[n_clips] : 0;
+    if (bad.empty())
+      bad = csr_check(frame_offsets, n_frames, 0, LIVE_MAX_FACES, {"frame_offsets", "frame", "detections"});
+    // (csr_check reads nothing of an array of no slices, but clips without frames still have a total)
+    if (bad.empty() && n_frames == 0 && frame_offsets[0] != 0) bad = "frame_offsets[0] must be 0";
+    if (!bad.empty()) return fail(h, FR_ERR_INVALID_ARGUMENT, bad);
+    const int total = frame_offsets[n_frames];
+    if (!clip_info || (total > 0 && (!bbox || !metrics || !track_id || !prev || !attempt || !best)))
+      return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer");
+  }
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  if (n_clips == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int* d_off[2];  // frame offsets, then clip offsets
+  if (int rc = stage_int32(h, s, {{frame_offsets, (size_t)n_frames + 1}, {clip_offsets, (size_t)n_clips + 1}}, d_off))
+    return rc;
+  const hipError_t e =
+      launch_live_tracks(bbox, metrics, d_off[0], d_off[1], n_clips, capture_q_limit(max_distance),
+                         recognition_interval, max_attempts, buffer_size, track_id, prev, attempt, best, clip_info, s);
+  if (e != hipSuccess) return launch_fail(h, "live tracks", e);
+  std::vector<int32_t> info((size_t)n_clips * 4);
+  FR_HIP(h, hipMemcpyAsync(info.data(), clip_info, info.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
+  for (int c = 0; c < n_clips; ++c)
+    if (info[(size_t)c * 4 + 3])
+      return fail(h, FR_ERR_UNSUPPORTED,
+                  "clip " + std::to_string(c) + ": a box coordinate beyond +-" + std::to_string(CAPTURE_COORD_MAX));
   return FR_OK;
 }
 

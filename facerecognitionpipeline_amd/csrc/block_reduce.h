@@ -1,5 +1,5 @@
 // Reductions over one workgroup of 256 threads (4 waves of 64), shared by track.hip, capture.hip,
-// gallery.hip, evaluate.hip and embed_misc.hip.
+// live.hip, gallery.hip, evaluate.hip and embed_misc.hip.
 //
 // The contract of every block_* function here, for all 256 threads of the block calling it:
 //   - a barrier comes before the write of `red` (4 elements of LDS), so LDS written before the

@@ -290,6 +290,20 @@ hipError_t launch_capture_tracks(const int* bbox, const double* metrics, const u
                                  long long q_limit, int target_frames, double min_quality_score, int save_partial,
                                  int* track_id, double* quality, int* slot, int* clip_info, hipStream_t s);
 
+// Live sessions (live.hip: LiveFaceRecognition._simple_track_assignment + LiveRecognitionTracker) of
+// n_clips CSR slices laid out as launch_capture_tracks takes them, at most LIVE_MAX_FACES detections
+// per frame and any number per clip; metrics [total][2] = det_score, blur_score.  q_limit as above.
+// track_id (from 0) / prev / attempt / best: [total], -1 for none, prev and best global detection
+// indices; clip_info: [n_clips][4] = tracks opened, candidates, frames, LIVE_ERR_* (0: none).
+constexpr int LIVE_MAX_FACES = 128;
+constexpr int LIVE_MAX_ATTEMPTS = 16;
+constexpr int LIVE_MAX_BUFFER = 64;
+enum LiveError : int { LIVE_ERR_COORD = 2 };  // CAPTURE_ERR_COORD's value: the same limit
+hipError_t launch_live_tracks(const int* bbox, const double* metrics, const int* frame_off, const int* clip_off,
+                              int n_clips, long long q_limit, int recognition_interval, int max_attempts,
+                              int buffer_size, int* track_id, int* prev, int* attempt, int* best, int* clip_info,
+                              hipStream_t s);
+
 // Model evaluation (evaluate.hip: the notebook's cosine_similarity / aggregate_* / identify_probe /
 // compute_rank_metrics and the threshold loops of evaluate_*_comprehensive).
 constexpr int EVAL_MAX_ROWS = 1024;      // gallery rows of one identity

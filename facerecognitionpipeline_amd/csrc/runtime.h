@@ -3,7 +3,7 @@
 //   frhip_runtime.cpp  the public fr_* C API (include/frhip.h): model, gallery rows, match, align,
 //                      detect, settings, profiling
 //   batch_ops.cpp      the fr_* calls over CSR batches: templates, track consensus, capture
-//                      sessions, identity scores, probe evaluation
+//                      and live sessions, identity scores, probe evaluation
 //   finalize.cpp       handle and entry-point helpers, state-dict schema, BatchNorm folding, arenas,
 //                      workspace
 //   conv_dispatch.cpp  run_conv and its kernel-selection rules
@@ -399,7 +399,7 @@ int ensure_winograd(fr_handle* h);
 int finalize_model(fr_handle* h);
 
 // batch_ops.cpp
-// fr_capture_tracks' match threshold: the smallest integer q >= 0 with sqrt(q / 4.0) >= max_distance
+// fr_capture_tracks' and fr_live_tracks' match threshold: the smallest integer q >= 0 with sqrt(q / 4.0) >= max_distance
 // in double (q = 4 x a squared centroid distance), so that q < q_limit is the reference's
 // `distance < max_distance`; 0 for max_distance <= 0 or NaN
 long long capture_q_limit(double max_distance);

@@ -14,6 +14,8 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
     rec_i, rec_d = torch.ops.frhip.track_consensus(idx, score, offsets, 0.55, 3, 0.5)  # [T,8] i32 / [T,2] f64
     tid, quality, slot, info = torch.ops.frhip.capture_tracks(bbox, metrics, valid, frame_offsets, clip_offsets,
                                                               30, 80.0, 12, 0.5, False)  # [N] x 3, [C,4] i32
+    tid, prev, attempt, best, info = torch.ops.frhip.live_tracks(bbox, det_blur, frame_offsets, clip_offsets,
+                                                                 100.0, 30, 3, 10)              # [N] x 4, [C,4] i32
     scores = torch.ops.frhip.identity_scores(q, gallery_rows, id_offsets, "mean", 3)   # [N, n_ids] f32
     rec_i, rec_f, counts = torch.ops.frhip.eval_probes(scores, true_id, thresholds)    # [N,4] x 2, [T,4] i64
 
@@ -63,7 +65,7 @@ _utility: Dict[torch.device, "_lib.Handle"] = {}
 
 def utility_handle(device) -> "_lib.Handle":
     """A model-less handle on ``device`` for the entry points that need no weights
-    (``augment_faces``, ``track_consensus``, ``capture_tracks``, ``identity_scores``, ``eval_probes``): one per device, created on first use."""
+    (``augment_faces``, ``track_consensus``, ``capture_tracks``, ``live_tracks``, ``identity_scores``, ``eval_probes``): one per device, created on first use."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
@@ -179,6 +181,24 @@ def _(bbox, metrics, valid, frame_offsets, clip_offsets, max_disappeared, max_di
     n, c = bbox.shape[0], max(len(clip_offsets) - 1, 0)
     return (bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((n,), dtype=torch.float64),
             bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((c, 4), dtype=torch.int32))
+
+
+@torch.library.custom_op("frhip::live_tracks", mutates_args=())
+def live_tracks(bbox: torch.Tensor, metrics: torch.Tensor, frame_offsets: List[int], clip_offsets: List[int],
+                max_distance: float, recognition_interval: int, max_attempts: int, buffer_size: int
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    if bbox.device.type != "cuda":
+        raise ValueError(f"bbox is on {bbox.device}: live_tracks runs on a HIP device (no CPU fallback)")
+    return utility_handle(bbox.device).live_tracks(bbox, metrics, frame_offsets, clip_offsets, max_distance,
+                                                   recognition_interval, max_attempts, buffer_size)
+
+
+@live_tracks.register_fake
+def _(bbox, metrics, frame_offsets, clip_offsets, max_distance, recognition_interval, max_attempts, buffer_size):
+    n, c = bbox.shape[0], max(len(clip_offsets) - 1, 0)
+    return (bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((n,), dtype=torch.int32),
+            bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((n,), dtype=torch.int32),
+            bbox.new_empty((c, 4), dtype=torch.int32))
 
 
 @torch.library.custom_op("frhip::identity_scores", mutates_args=())

@@ -234,6 +234,59 @@ int fr_capture_tracks(fr_handle* h,
                       int32_t* slot,     /* device [total] */
                       int32_t* clip_info /* device [n_clips][4] */, void* stream);
 
+/* Live sessions: LiveFaceRecognition._simple_track_assignment (face_recognition_live.py:249-285) and
+ * the gating and frame selection of LiveRecognitionTracker (:18-80) as process_frame drives them
+ * (:339-355), for n_clips independent sessions (cameras) in one launch.  Each session starts with no
+ * tracks and next_track_id = 0; a frame's 1-based frame_count is its index in the clip plus 1.
+ * Detections are a CSR over frames, frames a CSR over clips, as fr_capture_tracks takes them; a clip
+ * may hold any number of detections.
+ *   assignment  The live list is the previous frame's faces in that frame's detection order (the
+ *               reference's dict, replaced wholesale each frame: no disappearance tolerance).  Per
+ *               face the nearest live track by q = (sx_t - sx_d)^2 + (sy_t - sy_d)^2 with
+ *               sx = x1 + x2, sy = y1 + y2 in int64 (4 x the squared centroid distance, exact), among
+ *               the tracks with q < q_limit (fr_capture_tracks' q_limit of max_distance: the
+ *               reference's `distance < best_distance` from best_distance = max_distance, bit for
+ *               bit; max_distance <= 0 or NaN: nothing matches); equal q goes to the earlier list
+ *               position (the strict <).  The search reads the previous frame only.  A track goes to
+ *               the lowest-indexed face that chose it; every other face, one whose nearest track was
+ *               taken included (it does not fall back to another track in range), opens the next id
+ *               in detection order.  A track that no face chose is gone.
+ *               track_id[d] >= 0; prev[d] = the global index of the track's detection in the previous
+ *               frame, -1 for a new track.
+ *   gating      On a frame with frame_count % recognition_interval == 0, a track that was present on
+ *               a < max_attempts earlier such frames gets attempt[d] = a (should_recognize without
+ *               its "already recognised" test: the count is speculative, the caller drops the
+ *               attempts that follow a recognition); otherwise attempt[d] = -1.
+ *   selection   With attempt[d] >= 0, best[d] = the global index of the detection with the largest
+ *               key among the last min(run length, buffer_size) detections of d's prev chain, d
+ *               included; key = (double)det_score * min(blur_score / 100.0, 1.0) without contraction;
+ *               the oldest of equal keys (Python's max over the deque).  Otherwise best[d] = -1.
+ *               metrics must be finite.
+ * clip_info[c] = {tracks opened, candidates (attempt >= 0), frames, error}.  A clip with a coordinate
+ * beyond +-FR_CAPTURE_COORD_MAX gets {0, 0, 0, FR_LIVE_ERR_COORD}, track_id 0 and -1 in prev, attempt
+ * and best throughout, the other clips their results, and the call returns FR_ERR_UNSUPPORTED after
+ * its synchronisation.  Deterministic: integers but for the key.  Any handle will do, finalised or
+ * not.  Synchronises (the offsets are staged from the host).  n_clips == 0 is a no-op.  NULL buffers,
+ * n_clips < 0, offsets that do not start at 0 or that decrease, a frame over FR_LIVE_MAX_FACES,
+ * recognition_interval < 1, max_attempts outside [1, FR_LIVE_MAX_ATTEMPTS] and buffer_size outside
+ * [1, FR_LIVE_MAX_BUFFER] -> FR_ERR_INVALID_ARGUMENT (checked before the handle, so also reported for
+ * h == NULL). */
+#define FR_LIVE_MAX_FACES 128   /* detections in one frame */
+#define FR_LIVE_MAX_ATTEMPTS 16 /* max_attempts */
+#define FR_LIVE_MAX_BUFFER 64   /* buffer_size */
+#define FR_LIVE_ERR_COORD 2
+int fr_live_tracks(fr_handle* h,
+                   const int32_t* bbox,          /* device [total][4] x1 y1 x2 y2 (bbox.astype(int)) */
+                   const double* metrics,        /* device [total][2] det_score, blur_score */
+                   const int32_t* frame_offsets, /* host [n_frames + 1] */
+                   const int32_t* clip_offsets,  /* host [n_clips + 1] */
+                   int n_clips, double max_distance, int recognition_interval, int max_attempts, int buffer_size,
+                   int32_t* track_id, /* device [total] >= 0 */
+                   int32_t* prev,     /* device [total] */
+                   int32_t* attempt,  /* device [total] */
+                   int32_t* best,     /* device [total] */
+                   int32_t* clip_info /* device [n_clips][4] */, void* stream);
+
 /* Model evaluation, step 1 (evaluate_models_v2.ipynb: cosine_similarity, aggregate_max / _mean /
  * _topk as identify_probe applies them): the score of every probe against every identity of a
  * multi-embedding gallery.  Q: device [n][512]; E: device [G][512], an explicit matrix (the handle's

@@ -83,6 +83,18 @@ stored to pin them.
   ``compute_quality_score`` and saved ``frame_NNN`` number of every detection and the
   ``metadata.json`` numbers of every saved track.  scipy (``cdist``) is the installed one.
 
+* ``live_tracks.npz`` — the reference ``LiveFaceRecognition.process_frame`` (face_recognition_live.py:
+  320-414) with its ``LiveRecognitionTracker``, ``_update_attendance`` and ``_finalize_session``, on the
+  hand-built and seeded sessions of ``tests/_live_cases.py``.  The object is built without its
+  constructor (which loads models); its processor replays the session's detections, its embedder
+  returns the prepared unit vector of the crop it is handed, its gallery is the reference
+  ``GalleryManager`` over basis-vector templates.  ``performance_monitor_server`` is supplied as a
+  stub: the reference imports a ``PerformanceMonitor`` name that module does not define, and
+  monitoring is off.  Per session: the boxes, metrics, frame offsets, plans and settings, and the
+  reference's track id of every detection, its attempt log (tick detection, track, attempt number,
+  best detection, top-3 students and scores), ``attendance.json`` without its clock and folder
+  fields, and the statistics of ``session.json``.
+
 * ``evaluate.npz`` — the evaluation functions of ``evaluate_models_v2.ipynb`` (``cosine_similarity``,
   ``compute_all_similarities``, ``aggregate_*``, ``identify_probe``, ``compute_rank_metrics``,
   ``compute_dprime``, ``bootstrap_confidence_interval`` and the four ``evaluate_*_comprehensive``).  The
@@ -97,7 +109,7 @@ stored to pin them.
   ``facerecognitionpipeline_amd.evaluate_models`` reproduce the reference bit for bit on ``exact``,
   and that ``eval_probes_host`` reproduces its records and counts on every recorded score matrix.
 
-Usage: ``python tools/make_golden.py [embed] [c3] [resize] [backups] [refpkl] [gate] [image] [track] [capture] [evaluate] [dropin]``
+Usage: ``python tools/make_golden.py [embed] [c3] [resize] [backups] [refpkl] [gate] [image] [track] [capture] [live] [evaluate] [dropin]``
 (no argument: all).
 """
 from __future__ import annotations
@@ -216,7 +228,7 @@ def main() -> None:
     if not os.path.isdir(REF):
         raise SystemExit("reference not present; golden files are generated in the build container only")
     parts = set(sys.argv[1:]) or {"embed", "c3", "resize", "backups", "refpkl", "gate", "image", "track",
-                                     "capture", "evaluate", "dropin"}
+                                     "capture", "live", "evaluate", "dropin"}
     os.makedirs(OUT, exist_ok=True)
     tmp = tempfile.mkdtemp(prefix="frgolden_")
     with open(os.path.join(tmp, "cv2.py"), "w") as f:
@@ -613,6 +625,113 @@ def main() -> None:
         assert reached >= CC.REQUIRED, sorted(CC.REQUIRED - reached)
         np.savez_compressed(os.path.join(OUT, "capture_tracks.npz"), **out)
         print("capture", len(built), "sessions;", os.path.getsize(os.path.join(OUT, "capture_tracks.npz")), "bytes")
+
+    if "live" in parts:
+        import functools
+        from datetime import datetime
+        with open(os.path.join(tmp, "performance_monitor_server.py"), "w") as f:
+            f.write("class PerformanceMonitor:\n    def __init__(self, *a, **k):\n"
+                    "        raise RuntimeError('stub: monitoring is off for the golden files')\n")
+        import face_recognition_live as ref_live  # reference module
+        import tests._live_cases as LC
+        from facerecognitionpipeline_amd import face_recognition_live as ours
+
+        gallery_dir = os.path.join(tmp, "live_gallery")
+        with quiet():
+            gm = ref_gm.GalleryManager(gallery_path=os.path.join(gallery_dir, "students.pkl"))
+            for sid, name, t in zip(LC.STUDENT_IDS, LC.STUDENT_NAMES, LC.templates()):
+                gm.add_student(sid, name, t)
+        host_gallery = LC.HostGallery()
+        built = LC.build_sessions()
+        out = {"n_sessions": np.int32(len(built))}
+        reached = set()
+        for s, sess in enumerate(built):
+            bbox, metrics, offsets, plan_student, plan_score = LC.arrays(sess)
+            assert 12 <= len(offsets) - 1 <= 40 and max(np.diff(offsets)) <= 8, (s, len(offsets) - 1)
+            d = {"bbox": bbox, "metrics": metrics, "frame_offsets": offsets, "plan_student": plan_student,
+                 "plan_score": plan_score}
+            live = ref_live.LiveFaceRecognition.__new__(ref_live.LiveFaceRecognition)
+            live.similarity_threshold = sess["similarity_threshold"]
+            live.recognition_interval = sess["recognition_interval"]
+            live.max_recognition_attempts = sess["max_attempts"]
+            live.face_processor = LC.ReplayProcessor(d)
+            live.embedder = LC.PlanEmbedder(d)
+            live.gallery = gm
+            live.session_name = f"live_{s}"
+            live.session_dir = os.path.join(tmp, "live_sessions", live.session_name)
+            live.perf_monitor = None
+            live.tracker = ref_live.LiveRecognitionTracker(recognition_interval=sess["recognition_interval"],
+                                                           max_attempts=sess["max_attempts"],
+                                                           buffer_size=sess["buffer_size"])
+            live.recognized_faces_dir = os.path.join(live.session_dir, "recognized_faces")
+            live.unrecognized_faces_dir = os.path.join(live.session_dir, "unrecognized_faces")
+            os.makedirs(live.recognized_faces_dir)
+            os.makedirs(live.unrecognized_faces_dir)
+            live.auto_snapshot = False
+            live.session_start = datetime.now()
+            live.frame_count = live.total_faces_detected = live.total_recognition_attempts = 0
+            live.active_tracks, live.next_track_id = {}, 0
+            # max_distance is a default argument of _simple_track_assignment, which process_frame leaves alone
+            live._simple_track_assignment = functools.partial(live._simple_track_assignment,
+                                                              max_distance=sess["max_distance"])
+            with quiet():
+                live._init_session_files()
+                ids, log = LC.drive(live, d)
+                live._finalize_session()
+            assert all(e[4] is not None for e in log), s
+            rows, top_idx, top_score = LC.log_arrays(log)
+            with open(os.path.join(live.session_dir, "attendance.json")) as f:
+                attendance = LC.strip(json.load(f))
+            with open(os.path.join(live.session_dir, "session.json")) as f:
+                statistics = json.load(f)["statistics"]
+            statistics.pop("average_fps")
+            assert statistics["total_recognition_attempts"] == len(log), s
+            # the host statement of the kernel's contract is the reference, or the fixture is not written
+            trace = set()
+            kernel = {k: sess[k] for k in LC.SETTINGS if k != "similarity_threshold"}
+            h_ids, h_prev, h_attempt, h_best, h_info = ours.live_tracks_host(bbox, metrics, offsets, trace=trace, **kernel)
+            assert np.array_equal(h_ids, ids), s
+            h_log, h_events = ours.resolve_attempts(h_ids.tolist(), h_attempt, h_best, LC.recognise_with(d, host_gallery),
+                                                    sess["similarity_threshold"], sess["max_attempts"], trace=trace)
+            assert [(e["det"], e["track"], e["attempt"], e["best"]) for e in h_log] == [tuple(r) for r in rows.tolist()], s
+            assert [[m[2] for m in e["matches"]] for e in h_log] == top_score.tolist(), s
+            assert [[LC.STUDENT_IDS.index(m[0]) for m in e["matches"]] for e in h_log] == top_idx.tolist(), s
+            assert h_info == [int(ids.max()) + 1 if len(ids) else 0, int((h_attempt >= 0).sum()), len(offsets) - 1, 0], s
+            assert len(h_events) == sum(1 for e in log if e[4]["recognized"] or e[2] + 1 >= sess["max_attempts"]), s
+            # and the mirror classes give the same files
+            mine = ours.LiveFaceRecognition(similarity_threshold=sess["similarity_threshold"],
+                                            output_dir=os.path.join(tmp, "live_mirror"), session_name=f"live_{s}",
+                                            recognition_interval=sess["recognition_interval"],
+                                            max_recognition_attempts=sess["max_attempts"],
+                                            frame_buffer_size=sess["buffer_size"], processor=LC.ReplayProcessor(d),
+                                            embedder=LC.PlanEmbedder(d), gallery=host_gallery, verbose=False)
+            mine.max_distance = sess["max_distance"]
+            mine.trace = trace
+            m_ids, m_log = LC.drive(mine, d)
+            assert np.array_equal(m_ids, ids) and [e[:4] for e in m_log] == [e[:4] for e in log], s
+            with open(os.path.join(mine.session_dir, "attendance.json")) as f:
+                assert LC.strip(json.load(f)) == attendance, s
+            m_stats = mine._finalize_session()["statistics"]
+            m_stats.pop("average_fps")
+            assert m_stats == statistics, (s, m_stats, statistics)
+            reached |= trace
+            for name, v in (("track_id", ids), ("log", rows), ("log_top_idx", top_idx), ("log_top_score", top_score),
+                            ("attendance", np.array(json.dumps(attendance))),
+                            ("statistics", np.array(json.dumps(statistics))),
+                            ("max_distance", np.float64(sess["max_distance"])),
+                            ("recognition_interval", np.int32(sess["recognition_interval"])),
+                            ("max_attempts", np.int32(sess["max_attempts"])),
+                            ("buffer_size", np.int32(sess["buffer_size"])),
+                            ("similarity_threshold", np.float64(sess["similarity_threshold"]))):
+                d[name] = v
+            for name, v in d.items():
+                out[f"s{s}_{name}"] = v
+            print("live session", s, "frames", len(offsets) - 1, "detections", len(ids), "tracks", h_info[0],
+                  "attempts", len(log), "recognized", len(attendance["recognized"]), "unrecognized",
+                  len(attendance["unrecognized"]), sorted(trace))
+        assert reached >= LC.REQUIRED, sorted(LC.REQUIRED - reached)
+        np.savez_compressed(os.path.join(OUT, "live_tracks.npz"), **out)
+        print("live", len(built), "sessions;", os.path.getsize(os.path.join(OUT, "live_tracks.npz")), "bytes")
 
     if "evaluate" in parts:
         sys.path.insert(0, os.path.join(REPO, "tests"))
