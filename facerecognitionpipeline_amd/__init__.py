@@ -9,7 +9,7 @@ fallback.
 from .arch import block_specs, flop_per_face, state_dict_schema  # noqa: F401
 
 __all__ = ["FaceEmbedder", "GalleryManager", "FaceMatcher", "StudentEnrollment", "SimpleTracker", "FrameAccumulator",
-           "CameraFaceCapture", "LiveRecognitionTracker", "LiveFaceRecognition", "block_specs", "flop_per_face", "state_dict_schema"]
+           "CameraFaceCapture", "LiveRecognitionTracker", "LiveFaceRecognition", "DatasetPreprocessor", "ProbeSegmenter", "block_specs", "flop_per_face", "state_dict_schema"]
 
 
 def __getattr__(name):
@@ -31,4 +31,10 @@ def __getattr__(name):
     if name in ("LiveRecognitionTracker", "LiveFaceRecognition"):
         from . import face_recognition_live
         return getattr(face_recognition_live, name)
+    if name == "DatasetPreprocessor":
+        from .dataset_preprocessor import DatasetPreprocessor
+        return DatasetPreprocessor
+    if name == "ProbeSegmenter":
+        from .segment_dataset import ProbeSegmenter
+        return ProbeSegmenter
     raise AttributeError(name)

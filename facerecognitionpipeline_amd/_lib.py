@@ -55,6 +55,8 @@ _SIGNATURES = {
     "fr_warp_affine": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P]),
     "fr_blur_scores": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "fr_detect": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P]),
+    "fr_detect_images": (_I, [_P, _P, _P, _I, ctypes.c_float, _I, _P, _P, _P]),
+    "fr_align_images": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
     "fr_set_precision": (_I, [_P, _I]),
     "fr_set_conv_algorithm": (_I, [_P, _I]),
     "fr_set_graph_batch": (_I, [_P, _I]),
@@ -458,6 +460,54 @@ class Handle:
                                   int(max_faces), dets.ctypes.data, counts.ctypes.data, stream_of(self.device)),
               self.h)
         return dets, counts
+
+    def _image_list(self, images):
+        """A list of uint8 [H,W,3] device tensors -> (contiguous tensors on the handle's device, host
+        pointer array uint64 [n], host sizes int32 [n,2]) as fr_detect_images / fr_align_images take them."""
+        import numpy as np
+        kept = []
+        for i, im in enumerate(images):
+            if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+                raise ValueError(f"image {i}: expected a uint8 [H,W,3] RGB tensor")
+            kept.append(im.to(self.device).contiguous())
+        ptrs = np.array([im.data_ptr() if im.numel() else 0 for im in kept], dtype=np.uint64)
+        sizes = np.array([[im.shape[0], im.shape[1]] for im in kept], dtype=np.int32).reshape(-1, 2)
+        return kept, ptrs, sizes
+
+    def detect_images(self, images, det_thresh: float = 0.5, max_faces: int = 256):
+        """``detect`` for a list of uint8 [H,W,3] RGB device tensors of different sizes, in one call
+        (chunks of the handle's max_frames, per-image letterbox geometry: include/frhip.h,
+        fr_detect_images) -> (dets f32 [n,max_faces,15], counts int32 [n]), rows as ``detect`` gives them."""
+        import numpy as np
+        kept, ptrs, sizes = self._image_list(images)
+        n = len(kept)
+        dets = np.zeros((n, max(int(max_faces), 0), 15), dtype=np.float32)
+        counts = np.zeros(n, dtype=np.int32)
+        check(self._lib.fr_detect_images(self.h, ptrs.ctypes.data, sizes.ctypes.data, n, float(det_thresh),
+                                         int(max_faces), dets.ctypes.data, counts.ctypes.data,
+                                         stream_of(self.device)), self.h)
+        return dets, counts
+
+    def align_images(self, images, landmarks, face_image, out_size: int, out: torch.Tensor):
+        """``align_faces`` for faces of different images: ``images`` a list of uint8 [H,W,3] device
+        tensors, ``landmarks`` host float32 [n,5,2], ``face_image`` int32 [n] (the image of each face)
+        -> out uint8 [n,S,S,3] on the device, in one launch; returns tforms float64 [n,2,3]."""
+        import numpy as np
+        kept, ptrs, sizes = self._image_list(images)
+        lm = np.ascontiguousarray(landmarks, dtype=np.float32).reshape(-1, 5, 2)
+        fi = np.ascontiguousarray(face_image, dtype=np.int32).reshape(-1)
+        n = lm.shape[0]
+        if fi.shape[0] != n:
+            raise ValueError(f"face_image names {fi.shape[0]} faces, landmarks {n}")
+        S = int(out_size)
+        if (out.dtype != torch.uint8 or tuple(out.shape) != (n, S, S, 3) or out.device != self.device
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 {[n, S, S, 3]} tensor on {self.device}")
+        tf = np.empty((n, 2, 3), dtype=np.float64)
+        check(self._lib.fr_align_images(self.h, ptrs.ctypes.data, sizes.ctypes.data, len(kept), lm.ctypes.data,
+                                        fi.ctypes.data, n, S, ptr(out) if n else None, tf.ctypes.data,
+                                        stream_of(self.device)), self.h)
+        return tf
 
     def set_precision(self, mode: str) -> None:
         modes = {"fp32": 0, "f32": 0, "bf16x3": 1}

@@ -18,6 +18,24 @@
 
 namespace frhip {
 
+// Output pixel pix of one S x S crop: the inverse map m applied to a frame of H x W, 3 channels to o.
+__device__ __forceinline__ void warp_pixel(const uint8_t* __restrict__ frame, int H, int W, const double* m, int S,
+                                           int pix, uint8_t* __restrict__ o) {
+  const int oy = pix / S, ox = pix - oy * S;
+  const WarpTap t = warp_tap(m, warp_row(m, oy), ox);
+  const int sx = t.sx, sy = t.sy;
+  const bool in_x0 = (unsigned)sx < (unsigned)W, in_x1 = (unsigned)(sx + 1) < (unsigned)W;
+  const bool in_y0 = (unsigned)sy < (unsigned)H, in_y1 = (unsigned)(sy + 1) < (unsigned)H;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int p00 = (in_y0 && in_x0) ? frame[((long long)sy * W + sx) * 3 + c] : 0;
+    const int p01 = (in_y0 && in_x1) ? frame[((long long)sy * W + sx + 1) * 3 + c] : 0;
+    const int p10 = (in_y1 && in_x0) ? frame[((long long)(sy + 1) * W + sx) * 3 + c] : 0;
+    const int p11 = (in_y1 && in_x1) ? frame[((long long)(sy + 1) * W + sx + 1) * 3 + c] : 0;
+    o[c] = warp_blend(t, p00, p01, p10, p11);
+  }
+}
+
 // One thread per output pixel (all channels); blockIdx.y = face.
 // Maps come from device memory (minv) or, for up to WARP_MAPS_BY_VALUE faces, by value in the
 // kernel arguments (no H2D copy, so the caller needs no stream sync to keep a host buffer alive).
@@ -27,21 +45,19 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const uint8_t* __restr
   const int face = blockIdx.y;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   if (pix >= S * S) return;
-  const int oy = pix / S, ox = pix - oy * S;
   const double* m = minv ? minv + face * 6 : maps.m[face];
-  const WarpTap t = warp_tap(m, warp_row(m, oy), ox);
-  const int sx = t.sx, sy = t.sy;
-  const bool in_x0 = (unsigned)sx < (unsigned)W, in_x1 = (unsigned)(sx + 1) < (unsigned)W;
-  const bool in_y0 = (unsigned)sy < (unsigned)H, in_y1 = (unsigned)(sy + 1) < (unsigned)H;
-  uint8_t* o = out + ((long long)face * S * S + pix) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int p00 = (in_y0 && in_x0) ? frame[((long long)sy * W + sx) * 3 + c] : 0;
-    const int p01 = (in_y0 && in_x1) ? frame[((long long)sy * W + sx + 1) * 3 + c] : 0;
-    const int p10 = (in_y1 && in_x0) ? frame[((long long)(sy + 1) * W + sx) * 3 + c] : 0;
-    const int p11 = (in_y1 && in_x1) ? frame[((long long)(sy + 1) * W + sx + 1) * 3 + c] : 0;
-    o[c] = warp_blend(t, p00, p01, p10, p11);
-  }
+  warp_pixel(frame, H, W, m, S, pix, out + ((long long)face * S * S + pix) * 3);
+}
+
+// The ragged form (fr_align_images): face blockIdx.x reads its own frame, size and map from its
+// descriptor; blockIdx.y = block of 256 output pixels (the face count rides on grid x: no 65535 limit).
+__global__ __launch_bounds__(256) void warp_affine_images_kernel(const WarpFace* __restrict__ faces, int S,
+                                                                 uint8_t* __restrict__ out) {
+  const int face = blockIdx.x;
+  const int pix = blockIdx.y * 256 + threadIdx.x;
+  if (pix >= S * S) return;
+  const WarpFace* d = faces + face;
+  warp_pixel(d->src, d->H, d->W, d->minv, S, pix, out + ((long long)face * S * S + pix) * 3);
 }
 
 hipError_t launch_warp_affine(const uint8_t* frame, int H, int W, const double* minv, int n, int S, uint8_t* out,
@@ -61,6 +77,14 @@ hipError_t launch_warp_affine_by_value(const uint8_t* frame, int H, int W, const
     for (int j = 0; j < 6; ++j) maps.m[f][j] = host_minv[f * 6 + j];
   hipLaunchKernelGGL(warp_affine_kernel, dim3((S * S + 255) / 256, n), dim3(256), 0, s, frame, H, W,
                      (const double*)nullptr, maps, S, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_warp_affine_images(const WarpFace* faces, int n, int S, uint8_t* out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int blocks = (S * S + 255) / 256;
+  if (S < 1 || blocks > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(warp_affine_images_kernel, dim3(n, blocks), dim3(256), 0, s, faces, S, out);
   return hipGetLastError();
 }
 

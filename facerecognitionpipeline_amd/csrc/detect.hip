@@ -3,7 +3,8 @@
 // pyramid itself runs on the implicit-GEMM MFMA kernel (detector.cpp); these are the
 // HBM-bound pieces around it:
 //
-//   letterbox_kernel   cv2.resize(INTER_LINEAR) of each frame into the top-left of a
+//   letterbox_kernel   (and letterbox_images_kernel, for images of different sizes)
+//                      cv2.resize(INTER_LINEAR) of each frame into the top-left of a
 //                      zero det_w x det_h canvas, in OpenCV's fixed point (11-bit
 //                      coefficients from the host; SSE2 vertical rounding for the
 //                      vectorised part of each row, scalar rounding for its tail)
@@ -24,17 +25,13 @@ namespace frhip {
 // One thread per 4 consecutive canvas bytes of a row (one 32-bit store; a row is dw * 3 bytes,
 // a multiple of 4 for the detector's 640-wide canvas -- launch_letterbox checks), 32-bit index
 // arithmetic.  (One thread per byte with 64-bit div / mod took 114 us per 32-frame batch.)
-__global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restrict__ frames, int H, int W,
-                                                        const int* __restrict__ xtab, const int* __restrict__ ytab,
-                                                        int new_w, int new_h, int simd_end, int dw, int dh,
-                                                        uint8_t* __restrict__ out) {
-  const int f = blockIdx.y;
-  const int e4 = blockIdx.x * 256 + threadIdx.x;  // 4-byte group of the canvas
-  const int row = dw * 3, row4 = row / 4;
-  if (e4 >= dh * row4) return;
+// letterbox_group: the 4 bytes of group e4 of one frame's canvas; shared by the one-size kernel
+// (geometry in the kernel arguments) and the ragged one (geometry per frame in device memory).
+__device__ __forceinline__ unsigned letterbox_group(const uint8_t* __restrict__ src, int W,
+                                                    const int* __restrict__ xtab, const int* __restrict__ ytab,
+                                                    int new_w, int new_h, int simd_end, int row4, int e4) {
   const int y = e4 / row4;
   const int ex0 = (e4 - y * row4) * 4;
-  const uint8_t* src = frames + (long long)f * H * W * 3;
   unsigned packed = 0;
   if (y < new_h) {
     const int ys0 = ytab[4 * y], ys1 = ytab[4 * y + 1], b0 = ytab[4 * y + 2], b1 = ytab[4 * y + 3];
@@ -59,7 +56,34 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
       packed |= v << (8 * q);
     }
   }
-  reinterpret_cast<unsigned*>(out + (long long)f * dh * row)[e4] = packed;
+  return packed;
+}
+
+__global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restrict__ frames, int H, int W,
+                                                        const int* __restrict__ xtab, const int* __restrict__ ytab,
+                                                        int new_w, int new_h, int simd_end, int dw, int dh,
+                                                        uint8_t* __restrict__ out) {
+  const int f = blockIdx.y;
+  const int e4 = blockIdx.x * 256 + threadIdx.x;  // 4-byte group of the canvas
+  const int row = dw * 3, row4 = row / 4;
+  if (e4 >= dh * row4) return;
+  const uint8_t* src = frames + (long long)f * H * W * 3;
+  reinterpret_cast<unsigned*>(out + (long long)f * dh * row)[e4] =
+      letterbox_group(src, W, xtab, ytab, new_w, new_h, simd_end, row4, e4);
+}
+
+// The ragged form (fr_detect_images): frame f is an image of its own size at its own address, with
+// its own resize tables (at tabs + xtab / ytab) and SIMD / scalar rounding split.
+__global__ __launch_bounds__(256) void letterbox_images_kernel(const LetterboxImage* __restrict__ imgs,
+                                                               const int* __restrict__ tabs, int dw, int dh,
+                                                               uint8_t* __restrict__ out) {
+  const int f = blockIdx.y;
+  const int e4 = blockIdx.x * 256 + threadIdx.x;
+  const int row = dw * 3, row4 = row / 4;
+  if (e4 >= dh * row4) return;
+  const LetterboxImage im = imgs[f];
+  reinterpret_cast<unsigned*>(out + (long long)f * dh * row)[e4] =
+      letterbox_group(im.src, im.W, tabs + im.xtab, tabs + im.ytab, im.new_w, im.new_h, im.simd_end, row4, e4);
 }
 
 // One block per (frame, output row); thread t: channel group t & 3 (8 channels), pixels (t >> 2) + 64 j.
@@ -229,7 +253,7 @@ __global__ __launch_bounds__(256) void decode_kernel(DetDecodeParams p) {
   const float* h = p.head[lv] + ((long long)f * p.hw[lv] + loc) * 32;
   const int gy = loc / Wl, gx = loc - gy * Wl;
   const float cx = (float)gx * stride, cy = (float)gy * stride;
-  const float ds = p.det_scale;
+  const float ds = p.det_scales ? p.det_scales[f] : p.det_scale;
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
     const float score = 1.0f / (1.0f + expf(-h[a]));
@@ -336,6 +360,17 @@ hipError_t launch_letterbox(const uint8_t* frames, int n, int H, int W, const in
   if ((dw * 3) % 4 || elems >= (1ll << 31) || (reinterpret_cast<uintptr_t>(out) & 3)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(letterbox_kernel, dim3((unsigned)((elems / 4 + 255) / 256), n), dim3(256), 0, s, frames, H, W,
                      xtab, ytab, new_w, new_h, simd_end, dw, dh, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_letterbox_images(const LetterboxImage* imgs, const int* tabs, int n, int dw, int dh, uint8_t* out,
+                                   hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const long long elems = (long long)dh * dw * 3;
+  if ((dw * 3) % 4 || elems >= (1ll << 31) || n > 65535 || (reinterpret_cast<uintptr_t>(out) & 3))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(letterbox_images_kernel, dim3((unsigned)((elems / 4 + 255) / 256), n), dim3(256), 0, s, imgs,
+                     tabs, dw, dh, out);
   return hipGetLastError();
 }
 

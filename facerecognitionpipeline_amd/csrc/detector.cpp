@@ -67,9 +67,14 @@ struct Detector {
   int dets_cap = 0;
   bool row_reduce = true;  // row_plan (frt_set_detector_row_reduction switches it off for A/B)
   std::vector<int> htabs;
+  // fr_detect_images: one chunk's image descriptors, scales and resize tables, host and device
+  std::vector<char> himgs;
+  void* imgs = nullptr;
+  size_t imgs_cap = 0;
   ~Detector() {
     (void)hipFree(arena);
     (void)hipFree(ws);
+    (void)hipFree(imgs);
   }
 };
 
@@ -464,10 +469,9 @@ void row_plan(int new_h, int DH, Geometry& g) {
   g.at2 = a;
 }
 
-// Letterbox geometry (scrfd.py detect; Python floats are doubles) and the resize tables.
-int setup_geometry(fr_handle* h, int height, int width, Geometry& g, hipStream_t s) {
-  Detector* d = h->det;
-  const int DW = d->det_w, DH = d->det_h;
+// Letterbox size and scale of a height x width frame (scrfd.py detect; Python floats are doubles);
+// false when the frame is too small to letterbox.
+bool letterbox_size(int height, int width, int DW, int DH, Geometry& g) {
   const double imr = (double)height / width, mr = (double)DH / DW;
   if (imr > mr) {
     g.new_h = DH;
@@ -476,31 +480,93 @@ int setup_geometry(fr_handle* h, int height, int width, Geometry& g, hipStream_t
     g.new_w = DW;
     g.new_h = (int)(g.new_w * imr);
   }
-  if (g.new_w < 1 || g.new_h < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "frame too small to letterbox");
+  if (g.new_w < 1 || g.new_h < 1) return false;
   g.det_scale = (double)g.new_h / height;
+  g.simd_end = resize_simd_end(g.new_w * 3);
+  return true;
+}
+
+// Letterbox geometry and the resize tables of one frame size.
+int setup_geometry(fr_handle* h, int height, int width, Geometry& g, hipStream_t s) {
+  Detector* d = h->det;
+  const int DH = d->det_h;
+  if (!letterbox_size(height, width, d->det_w, DH, g))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "frame too small to letterbox");
   d->htabs.assign((size_t)(g.new_w + g.new_h) * 4, 0);
   resize_axis_table(g.new_w, width, d->htabs.data());
   resize_axis_table(g.new_h, height, d->htabs.data() + 4 * g.new_w);
-  g.simd_end = resize_simd_end(g.new_w * 3);
   if (d->row_reduce) row_plan(g.new_h, DH, g);
   FR_HIP(h, hipMemcpyAsync(d->tabs, d->htabs.data(), d->htabs.size() * sizeof(int), hipMemcpyHostToDevice, s));
   return FR_OK;
 }
 
+// One chunk of fr_detect_images: B <= max_frames images of their own sizes (validated by the caller).
+// Stages the images' descriptors, scales and concatenated resize tables in one copy and letterboxes
+// them into d->canvas.  g gets the chunk's row plan: new_h is the largest of the chunk, so the rows
+// the plan skips are zero rows of every image's canvas.  *scales: device [B] det_scale per image.
+int letterbox_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int B, Geometry& g,
+                     const float** scales, hipStream_t s) {
+  Detector* d = h->det;
+  const int DW = d->det_w, DH = d->det_h;
+  std::vector<Geometry> gs(B);
+  size_t ints = 0;
+  int max_h = 0;
+  for (int i = 0; i < B; ++i) {
+    letterbox_size(sizes[2 * i], sizes[2 * i + 1], DW, DH, gs[i]);
+    ints += (size_t)(gs[i].new_w + gs[i].new_h) * 4;
+    max_h = std::max(max_h, gs[i].new_h);
+  }
+  // [B] LetterboxImage | [B] float | tables
+  const size_t scale_off = (size_t)B * sizeof(LetterboxImage), tab_off = scale_off + (size_t)B * sizeof(float);
+  d->himgs.assign(tab_off + ints * sizeof(int), 0);
+  auto* im = reinterpret_cast<LetterboxImage*>(d->himgs.data());
+  auto* sc = reinterpret_cast<float*>(d->himgs.data() + scale_off);
+  int* tabs = reinterpret_cast<int*>(d->himgs.data() + tab_off);
+  int at = 0;
+  for (int i = 0; i < B; ++i) {
+    const int height = sizes[2 * i], width = sizes[2 * i + 1];
+    im[i] = LetterboxImage{images[i], width, gs[i].new_w, gs[i].new_h, gs[i].simd_end, at, at + 4 * gs[i].new_w};
+    resize_axis_table(gs[i].new_w, width, tabs + im[i].xtab);
+    resize_axis_table(gs[i].new_h, height, tabs + im[i].ytab);
+    at += (gs[i].new_w + gs[i].new_h) * 4;
+    sc[i] = (float)gs[i].det_scale;
+  }
+  g = Geometry{};
+  g.new_h = max_h;
+  if (d->row_reduce) row_plan(max_h, DH, g);
+  if (int rc = ensure_buf(h, &d->imgs, &d->imgs_cap, d->himgs.size())) return rc;
+  FR_HIP(h, hipMemcpyAsync(d->imgs, d->himgs.data(), d->himgs.size(), hipMemcpyHostToDevice, s));
+  const char* base = static_cast<const char*>(d->imgs);
+  *scales = reinterpret_cast<const float*>(base + scale_off);
+  const hipError_t e =
+      launch_letterbox_images(reinterpret_cast<const LetterboxImage*>(base), reinterpret_cast<const int*>(base + tab_off),
+                              B, DW, DH - g.skip1, d->canvas, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("letterbox: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int forward_network(fr_handle* h, int B, const Geometry& g, hipStream_t s);
+
 // Letterbox + network for B <= max_frames frames; head maps land in d->hd[0..2].
 int forward_chunk(fr_handle* h, const uint8_t* fr, int B, int height, int width, const Geometry& g, hipStream_t s) {
   Detector* d = h->det;
-  const int DW = d->det_w, DH = d->det_h;
   const int* xtab = d->tabs;
   const int* ytab = d->tabs + 4 * g.new_w;
+  const hipError_t e = launch_letterbox(fr, B, height, width, xtab, ytab, g.new_w, g.new_h, g.simd_end, d->det_w,
+                                        d->det_h - g.skip1, d->canvas, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("letterbox: ") + hipGetErrorString(e));
+  return forward_network(h, B, g, s);
+}
+
+// The network on the B letterboxed canvases in d->canvas (DH - g.skip1 rows each).
+int forward_network(fr_handle* h, int B, const Geometry& g, hipStream_t s) {
+  Detector* d = h->det;
+  const int DW = d->det_w, DH = d->det_h;
   const int c0 = pad32(STEM / 2);
   // the stem and stage 1 run on a canvas of DH - skip1 rows, stage 2 on DH - skip2 (row_plan)
   const int Hc = DH - g.skip1;
   const int H0 = Hc / 2, W0 = DW / 2, H1 = H0 / 2, W1 = W0 / 2;
-  const int new_w = g.new_w, new_h = g.new_h, simd_end = g.simd_end;
-  hipError_t e = launch_letterbox(fr, B, height, width, xtab, ytab, new_w, new_h, simd_end, DW, Hc, d->canvas, s);
-  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("letterbox: ") + hipGetErrorString(e));
-  e = launch_det_stem(d->canvas, B, Hc, DW, c0, d->stem_w, d->stem_scale, d->stem_shift, d->big0, s);
+  hipError_t e = launch_det_stem(d->canvas, B, Hc, DW, c0, d->stem_w, d->stem_scale, d->stem_shift, d->big0, s);
   if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("det stem: ") + hipGetErrorString(e));
   int rc = dconv(h, d->stem1, d->big0, d->big1, B, H0, W0, EPI_AFFINE_PRELU, nullptr, s);
   if (rc) return rc;
@@ -597,61 +663,91 @@ int forward_chunk(fr_handle* h, const uint8_t* fr, int B, int height, int width,
 
 }  // namespace
 
+namespace {
+
+// decode + NMS of the B head maps in d->hd, then the detections of frames [off, off + B) to the host.
+// Decode divides by scales[b] (device, per frame) or, when scales is NULL, by det_scale.  `what` names
+// a frame in the DET_MAX_CANDIDATES error.  Synchronises.
+int postprocess_chunk(fr_handle* h, int B, int off, float det_scale, const float* scales, const char* what,
+                      float det_thresh, int max_faces, float* dets, int32_t* counts, hipStream_t s) {
+  Detector* d = h->det;
+  const int DW = d->det_w, DH = d->det_h;
+  const int lh[3] = {DH / 8, DH / 16, DH / 32}, lw[3] = {DW / 8, DW / 16, DW / 32};
+  const int fmax = std::min(max_faces, d->dets_cap);
+  FR_HIP(h, hipMemsetAsync(d->count, 0, B * sizeof(int), s));
+  DetDecodeParams dp{};
+  int base = 0;
+  for (int i = 0; i < 3; ++i) {
+    dp.head[i] = d->hd[i];
+    dp.hw[i] = lh[i] * lw[i];
+    dp.w[i] = lw[i];
+    dp.stride[i] = STRIDES[i];
+    dp.anchor_base[i] = base;
+    base += dp.hw[i] * 2;
+  }
+  dp.thresh = det_thresh;
+  dp.det_scale = det_scale;
+  dp.det_scales = scales;
+  dp.cap = DET_MAX_CANDIDATES;
+  dp.count = d->count;
+  dp.cand = d->cand;
+  hipError_t e = launch_decode(dp, B, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("decode: ") + hipGetErrorString(e));
+  e = launch_nms(d->cand, d->count, B, DET_MAX_CANDIDATES, 0.4f, d->dets_cap, d->dets, d->dets_count, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("nms: ") + hipGetErrorString(e));
+  std::vector<float> hbuf((size_t)B * d->dets_cap * 15);
+  std::vector<int> hcnt(B), hraw(B);
+  FR_HIP(h, hipMemcpyAsync(hbuf.data(), d->dets, hbuf.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  FR_HIP(h, hipMemcpyAsync(hcnt.data(), d->dets_count, B * sizeof(int), hipMemcpyDeviceToHost, s));
+  FR_HIP(h, hipMemcpyAsync(hraw.data(), d->count, B * sizeof(int), hipMemcpyDeviceToHost, s));
+  FR_HIP(h, hipStreamSynchronize(s));
+  for (int b = 0; b < B; ++b) {
+    if (hraw[b] > DET_MAX_CANDIDATES)
+      return fail(h, FR_ERR_UNSUPPORTED,
+                  std::string(what) + " " + std::to_string(off + b) + " has " + std::to_string(hraw[b]) +
+                      " anchors above det_thresh (limit " + std::to_string(DET_MAX_CANDIDATES) + ")");
+    counts[off + b] = hcnt[b];
+    const int k = std::min(hcnt[b], fmax);
+    std::memcpy(dets + ((size_t)(off + b) * max_faces) * 15, hbuf.data() + (size_t)b * d->dets_cap * 15,
+                (size_t)k * 15 * sizeof(float));
+  }
+  return FR_OK;
+}
+
+// The testing hooks' outputs: the n head maps of d->hd back to back and the full det_h-row canvases
+// (the rows row_plan skipped are zeros).  Synchronises.
+int copy_heads_canvas(fr_handle* h, int n, const Geometry& g, float* heads, uint8_t* canvas, hipStream_t s) {
+  Detector* d = h->det;
+  size_t off = 0;
+  for (int i = 0; i < 3; ++i) {
+    const size_t bytes = (size_t)n * (d->det_h >> (3 + i)) * (d->det_w >> (3 + i)) * 32 * sizeof(float);
+    FR_HIP(h, hipMemcpyAsync((char*)heads + off, d->hd[i], bytes, hipMemcpyDeviceToDevice, s));
+    off += bytes;
+  }
+  if (canvas) {
+    const size_t row = (size_t)d->det_w * 3, Hc = (size_t)(d->det_h - g.skip1);
+    FR_HIP(h, hipMemcpy2DAsync(canvas, d->det_h * row, d->canvas, Hc * row, Hc * row, n, hipMemcpyDeviceToDevice, s));
+    if (g.skip1)
+      FR_HIP(h, hipMemset2DAsync(canvas + Hc * row, d->det_h * row, 0, (size_t)g.skip1 * row, n, s));
+  }
+  FR_HIP(h, hipStreamSynchronize(s));
+  return FR_OK;
+}
+
+}  // namespace
+
 int detector_run(fr_handle* h, const uint8_t* frames, int n, int height, int width, float det_thresh, int max_faces,
                  float* dets, int32_t* counts, hipStream_t s) {
   Detector* d = h->det;
-  const int DW = d->det_w, DH = d->det_h;
   Geometry g;
   int rc = setup_geometry(h, height, width, g, s);
   if (rc) return rc;
-  const double det_scale = g.det_scale;
-  const int lh[3] = {DH / 8, DH / 16, DH / 32}, lw[3] = {DW / 8, DW / 16, DW / 32};
-  const int fmax = std::min(max_faces, d->dets_cap);
-  std::vector<float> hbuf;
-  std::vector<int> hcnt, hraw;
   for (int off = 0; off < n; off += d->max_frames) {
     const int B = std::min(d->max_frames, n - off);
     rc = forward_chunk(h, frames + (size_t)off * height * width * 3, B, height, width, g, s);
     if (rc) return rc;
-    hipError_t e;
-    // decode + NMS
-    FR_HIP(h, hipMemsetAsync(d->count, 0, B * sizeof(int), s));
-    DetDecodeParams dp{};
-    int base = 0;
-    for (int i = 0; i < 3; ++i) {
-      dp.head[i] = d->hd[i];
-      dp.hw[i] = lh[i] * lw[i];
-      dp.w[i] = lw[i];
-      dp.stride[i] = STRIDES[i];
-      dp.anchor_base[i] = base;
-      base += dp.hw[i] * 2;
-    }
-    dp.thresh = det_thresh;
-    dp.det_scale = (float)det_scale;
-    dp.cap = DET_MAX_CANDIDATES;
-    dp.count = d->count;
-    dp.cand = d->cand;
-    e = launch_decode(dp, B, s);
-    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("decode: ") + hipGetErrorString(e));
-    e = launch_nms(d->cand, d->count, B, DET_MAX_CANDIDATES, 0.4f, d->dets_cap, d->dets, d->dets_count, s);
-    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("nms: ") + hipGetErrorString(e));
-    hbuf.resize((size_t)B * d->dets_cap * 15);
-    hcnt.resize(B);
-    hraw.resize(B);
-    FR_HIP(h, hipMemcpyAsync(hbuf.data(), d->dets, hbuf.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    FR_HIP(h, hipMemcpyAsync(hcnt.data(), d->dets_count, B * sizeof(int), hipMemcpyDeviceToHost, s));
-    FR_HIP(h, hipMemcpyAsync(hraw.data(), d->count, B * sizeof(int), hipMemcpyDeviceToHost, s));
-    FR_HIP(h, hipStreamSynchronize(s));
-    for (int b = 0; b < B; ++b) {
-      if (hraw[b] > DET_MAX_CANDIDATES)
-        return fail(h, FR_ERR_UNSUPPORTED,
-                    "frame " + std::to_string(off + b) + " has " + std::to_string(hraw[b]) +
-                        " anchors above det_thresh (limit " + std::to_string(DET_MAX_CANDIDATES) + ")");
-      counts[off + b] = hcnt[b];
-      const int k = std::min(hcnt[b], fmax);
-      std::memcpy(dets + ((size_t)(off + b) * max_faces) * 15, hbuf.data() + (size_t)b * d->dets_cap * 15,
-                  (size_t)k * 15 * sizeof(float));
-    }
+    rc = postprocess_chunk(h, B, off, (float)g.det_scale, nullptr, "frame", det_thresh, max_faces, dets, counts, s);
+    if (rc) return rc;
   }
   return FR_OK;
 }
@@ -665,20 +761,57 @@ int detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int
   if (rc) return rc;
   rc = forward_chunk(h, frames, n, height, width, g, s);
   if (rc) return rc;
-  size_t off = 0;
-  for (int i = 0; i < 3; ++i) {
-    const size_t bytes = (size_t)n * (d->det_h >> (3 + i)) * (d->det_w >> (3 + i)) * 32 * sizeof(float);
-    FR_HIP(h, hipMemcpyAsync((char*)heads + off, d->hd[i], bytes, hipMemcpyDeviceToDevice, s));
-    off += bytes;
+  return copy_heads_canvas(h, n, g, heads, canvas, s);
+}
+
+int detector_check_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n) {
+  Detector* d = h->det;
+  for (int i = 0; i < n; ++i) {
+    const int height = sizes[2 * i], width = sizes[2 * i + 1];
+    if (!images[i]) return fail(h, FR_ERR_INVALID_ARGUMENT, "image " + std::to_string(i) + " is a NULL pointer");
+    if (height < 1 || height > FR_IMAGE_MAX_SIDE || width < 1 || width > FR_IMAGE_MAX_SIDE)
+      return fail(h, FR_ERR_INVALID_ARGUMENT,
+                  "image " + std::to_string(i) + " is " + std::to_string(height) + " x " + std::to_string(width) +
+                      " (each side must be in [1, " + std::to_string(FR_IMAGE_MAX_SIDE) + "])");
+    Geometry g;
+    if (!letterbox_size(height, width, d->det_w, d->det_h, g))
+      return fail(h, FR_ERR_INVALID_ARGUMENT, "image " + std::to_string(i) + " is too small to letterbox");
   }
-  if (canvas) {  // the full det_h-row canvases (the rows row_plan skipped are zeros)
-    const size_t row = (size_t)d->det_w * 3, Hc = (size_t)(d->det_h - g.skip1);
-    FR_HIP(h, hipMemcpy2DAsync(canvas, d->det_h * row, d->canvas, Hc * row, Hc * row, n, hipMemcpyDeviceToDevice, s));
-    if (g.skip1)
-      FR_HIP(h, hipMemset2DAsync(canvas + Hc * row, d->det_h * row, 0, (size_t)g.skip1 * row, n, s));
-  }
-  FR_HIP(h, hipStreamSynchronize(s));
   return FR_OK;
+}
+
+int detector_run_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float det_thresh,
+                        int max_faces, float* dets, int32_t* counts, hipStream_t s) {
+  Detector* d = h->det;
+  int rc = detector_check_images(h, images, sizes, n);  // all of them, before the first chunk runs
+  if (rc) return rc;
+  for (int off = 0; off < n; off += d->max_frames) {
+    const int B = std::min(d->max_frames, n - off);
+    Geometry g;
+    const float* scales = nullptr;
+    rc = letterbox_images(h, images + off, sizes + 2 * (size_t)off, B, g, &scales, s);
+    if (rc) return rc;
+    rc = forward_network(h, B, g, s);
+    if (rc) return rc;
+    rc = postprocess_chunk(h, B, off, 0.f, scales, "image", det_thresh, max_faces, dets, counts, s);
+    if (rc) return rc;
+  }
+  return FR_OK;
+}
+
+int detector_forward_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* heads,
+                            uint8_t* canvas, hipStream_t s) {
+  Detector* d = h->det;
+  if (n > d->max_frames) return fail(h, FR_ERR_INVALID_ARGUMENT, "n exceeds the handle's max_batch");
+  int rc = detector_check_images(h, images, sizes, n);
+  if (rc) return rc;
+  Geometry g;
+  const float* scales = nullptr;
+  rc = letterbox_images(h, images, sizes, n, g, &scales, s);
+  if (rc) return rc;
+  rc = forward_network(h, n, g, s);
+  if (rc) return rc;
+  return copy_heads_canvas(h, n, g, heads, canvas, s);
 }
 
 }  // namespace frhip_rt

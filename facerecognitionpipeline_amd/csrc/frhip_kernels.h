@@ -229,6 +229,15 @@ struct WarpMaps {
 hipError_t launch_warp_affine_by_value(const uint8_t* frame, int H, int W, const double* host_minv, int n, int S,
                                        uint8_t* out, hipStream_t s);
 
+// The same for n faces of different frames, in one launch for any n: face f warps its own frame by
+// its own inverse map; faces: device [n]; out: [n][S][S][3], S <= 4096.
+struct WarpFace {
+  const uint8_t* src;  // device uint8 [H][W][3]
+  int H, W;
+  double minv[6];
+};
+hipError_t launch_warp_affine_images(const WarpFace* faces, int n, int S, uint8_t* out, hipStream_t s);
+
 // Laplacian variance (numpy's summation order) of the gray image of n uint8 images [n][H][W][C]
 // (C = 3 / 4: RGB(A) -> gray; C = 1: gray) -> var[n] (double).  Images whose gray copy and
 // summation trees fit BLUR_LDS_MAX bytes of LDS take one block each; larger ones take three
@@ -335,6 +344,7 @@ struct DetDecodeParams {
   const float* head[3];  // per level [B][hw][32]
   int hw[3], w[3], stride[3], anchor_base[3];
   float thresh, det_scale;
+  const float* det_scales;  // device [B] per-frame scales (fr_detect_images), or NULL: det_scale for all
   int cap;
   int* count;   // [B] candidates found (may exceed cap)
   float* cand;  // [B][cap][16]: score, anchor (int bits), x1 y1 x2 y2, 5 x (x, y)
@@ -344,6 +354,15 @@ struct DetDecodeParams {
 // zero dw x dh canvases; xtab/ytab: device [new_w|new_h][4] = (src0, src1, w0, w1).
 hipError_t launch_letterbox(const uint8_t* frames, int n, int H, int W, const int* xtab, const int* ytab, int new_w,
                             int new_h, int simd_end, int dw, int dh, uint8_t* out, hipStream_t s);
+// The same for n images of different sizes (n <= 65535), each with its own geometry: imgs: device
+// [n]; tabs: device ints, image f's tables at tabs + xtab ([new_w][4]) and tabs + ytab ([new_h][4]).
+struct LetterboxImage {
+  const uint8_t* src;  // device uint8 [H][W][3]; the tables hold every row index, so H itself is not needed
+  int W, new_w, new_h, simd_end;
+  int xtab, ytab;  // offsets into tabs, in ints
+};
+hipError_t launch_letterbox_images(const LetterboxImage* imgs, const int* tabs, int n, int dw, int dh, uint8_t* out,
+                                   hipStream_t s);
 // (x - 127.5)/128 -> conv3x3 s2 p1 3->C (C % 8 == 0, <= 32; weights [27][C]) -> BN -> ReLU, NHWC.
 hipError_t launch_det_stem(const uint8_t* img, int n, int H, int W, int C, const float* w27xC, const float* scale,
                            const float* shift, float* y, hipStream_t s);

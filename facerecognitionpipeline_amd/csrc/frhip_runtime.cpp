@@ -399,6 +399,63 @@ int fr_detect(fr_handle* h, const uint8_t* frames, int n, int height, int width,
   return check_dev_err(h);  // detector_run synchronised its stream
 }
 
+int fr_detect_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float det_thresh,
+                     int max_faces, float* dets, int32_t* counts, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->detector) return fail(h, FR_ERR_STATE, "not a detector handle (fr_create(\"scrfd_10g\", \"scrfd\", ...))");
+  if (!h->finalized) return fail(h, FR_ERR_STATE, "model not finalised (fr_finalize)");
+  if (max_faces < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "max_faces must be at least 1");
+  if (n < 0 || (n > 0 && (!images || !sizes || !dets || !counts)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or NULL images / sizes / output buffers");
+  if (n == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  if (int rc = detector_run_images(h, images, sizes, n, det_thresh, max_faces, dets, counts, (hipStream_t)stream))
+    return rc;
+  return check_dev_err(h);  // detector_run_images synchronised its stream
+}
+
+int fr_align_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n_images,
+                    const float* landmarks, const int32_t* face_image, int n_faces, int out_size, uint8_t* out,
+                    double* tforms, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (n_faces < 0 || n_images < 0 || out_size <= 0 || out_size > 1024 ||
+      (n_faces > 0 && (!images || !sizes || !landmarks || !face_image || !out)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad alignment arguments");
+  if (n_faces == 0) return FR_OK;
+  for (int i = 0; i < n_images; ++i)
+    if (!images[i] || sizes[2 * i] <= 0 || sizes[2 * i + 1] <= 0)
+      return fail(h, FR_ERR_INVALID_ARGUMENT, "image " + std::to_string(i) + " is NULL or has a side < 1");
+  float tmpl[10];
+  reference_template(out_size, tmpl);
+  std::vector<WarpFace> faces((size_t)n_faces);
+  for (int f = 0; f < n_faces; ++f) {
+    const int i = face_image[f];
+    if (i < 0 || i >= n_images)
+      return fail(h, FR_ERR_INVALID_ARGUMENT,
+                  "face " + std::to_string(f) + " names image " + std::to_string(i) + " of " + std::to_string(n_images));
+    double Mf[6];
+    if (!fit_similarity(landmarks + (size_t)f * 10, tmpl, 5, Mf))
+      return fail(h, FR_ERR_INVALID_ARGUMENT, "similarity fit failed for face " + std::to_string(f));
+    if (tforms) memcpy(tforms + (size_t)f * 6, Mf, 6 * sizeof(double));
+    faces[f].src = images[i];
+    faces[f].H = sizes[2 * i];
+    faces[f].W = sizes[2 * i + 1];
+    invert_affine(Mf, faces[f].minv);
+  }
+  DeviceGuard dg(h->device);
+  const size_t bytes = faces.size() * sizeof(WarpFace);
+  int rc = ensure_buf(h, &h->align_m, &h->align_m_cap, bytes);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  FR_HIP(h, hipMemcpyAsync(h->align_m, faces.data(), bytes, hipMemcpyHostToDevice, s));
+  const hipError_t e = launch_warp_affine_images((const WarpFace*)h->align_m, n_faces, out_size, out, s);
+  if (e != hipSuccess) return launch_fail(h, "warp", e);
+  FR_HIP(h, hipStreamSynchronize(s));
+  return FR_OK;
+}
+
 int fr_set_precision(fr_handle* h, int mode) {
   if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
   std::lock_guard<std::mutex> lk(h->mu);

@@ -308,6 +308,16 @@ int frt_detector_forward(fr_handle* h, const uint8_t* frames, int n, int height,
   return detector_forward(h, frames, n, height, width, heads, canvas, (hipStream_t)stream);
 }
 
+int frt_detector_forward_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* heads,
+                                uint8_t* canvas, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->detector || !h->finalized) return fail(h, FR_ERR_STATE, "not a finalised detector handle");
+  if (n < 1 || !images || !sizes || !heads) return fail(h, FR_ERR_INVALID_ARGUMENT, "bad arguments");
+  DeviceGuard dg(h->device);
+  return detector_forward_images(h, images, sizes, n, heads, canvas, (hipStream_t)stream);
+}
+
 int frt_set_detector_row_reduction(fr_handle* h, int on) {
   if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
   std::lock_guard<std::mutex> lk(h->mu);

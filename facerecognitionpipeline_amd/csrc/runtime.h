@@ -194,7 +194,7 @@ struct fr_handle {
   size_t eval_ws_cap = 0;
 
   // alignment / quality workspace
-  void* align_m = nullptr;  // [n][6] inverse affine maps (double)
+  void* align_m = nullptr;  // [n][6] inverse affine maps (double), or fr_align_images' [n] WarpFace
   size_t align_m_cap = 0;
   void* blur_out = nullptr;  // [n] double
   size_t blur_out_cap = 0;
@@ -458,5 +458,12 @@ int detector_run(fr_handle* h, const uint8_t* frames, int n, int height, int wid
                  float* dets, int32_t* counts, hipStream_t s);
 int detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int width, float* heads,
                      uint8_t* canvas, hipStream_t s);
+// The same for n images of their own sizes (host arrays: images[n] device pointers, sizes[n][2] =
+// height, width), in chunks of max_frames with per-image letterbox geometry (frhip.h: fr_detect_images);
+// detector_forward_images runs one chunk as detector_run_images runs it.
+int detector_run_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float det_thresh,
+                        int max_faces, float* dets, int32_t* counts, hipStream_t s);
+int detector_forward_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* heads,
+                            uint8_t* canvas, hipStream_t s);
 
 }  // namespace frhip_rt

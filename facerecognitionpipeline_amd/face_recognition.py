@@ -14,6 +14,11 @@ gives a state dict in ``detector_arch`` keys; ``FaceProcessor`` also accepts
 any detector object with the reference's
 ``detect(image_rgb) -> [{'bbox','landmarks','det_score',...}]`` contract.
 
+Images of different sizes (a folder of photographs) go through ``detect_images`` /
+``align_images`` / ``FaceProcessor.process_images``: one detect call, one align launch and
+one blur call for the whole sequence (``fr_detect_images`` / ``fr_align_images``), per image
+the single-image arithmetic.
+
 Parity of the OpenCV arithmetic is UNPINNED (cv2 absent); the kernels are
 pinned bit-exactly to the restatement in ``oracle/align_ref.py``.
 """
@@ -79,6 +84,39 @@ class FaceAligner:
             tf = np.stack([affine_from_3_points(x[:3], self.template[:3]) for x in lm])
             self._ops.handle.warp_affine(frame, tf, S, out)
         return out
+
+    def align_images(self, images, landmarks_per_image, method: str = "similarity") -> torch.Tensor:
+        """``align_batch`` over images of different sizes in one launch: ``images`` a sequence of uint8
+        [H,W,3] frames (host arrays or device tensors), ``landmarks_per_image[i]`` the float32 [k_i,5,2]
+        landmarks of image i's faces (k_i may be 0) -> uint8 [sum k_i,S,S,3] on the GPU, image by image
+        in face order.  Any ``method`` but "similarity" runs ``align_batch`` per image."""
+        if len(images) != len(landmarks_per_image):
+            raise ValueError(f"{len(images)} images but landmarks for {len(landmarks_per_image)}")
+        dev, S = self._ops.device, self.output_size
+        frames = [_device_frame(im, dev) for im in images]
+        lms = [np.ascontiguousarray(lm, dtype=np.float32).reshape(-1, 5, 2) for lm in landmarks_per_image]
+        total = sum(lm.shape[0] for lm in lms)
+        if method != "similarity":
+            parts = [self.align_batch(f, lm, method) for f, lm in zip(frames, lms) if lm.shape[0]]
+            return torch.cat(parts) if parts else torch.empty((0, S, S, 3), dtype=torch.uint8, device=dev)
+        out = torch.empty((total, S, S, 3), dtype=torch.uint8, device=dev)
+        if total:
+            face_image = np.repeat(np.arange(len(lms), dtype=np.int32), [lm.shape[0] for lm in lms])
+            self._ops.handle.align_images(frames, np.concatenate(lms), face_image, S, out)
+        return out
+
+
+def _device_frame(image, device) -> torch.Tensor:
+    """A host array or device tensor, uint8 [H,W,3] or gray [H,W] (replicated to three channels, as
+    cv2.COLOR_GRAY2BGR does), as a contiguous uint8 [H,W,3] tensor on ``device``."""
+    if isinstance(image, torch.Tensor):
+        t = image
+        if t.dim() == 2:
+            t = t[:, :, None].expand(-1, -1, 3)
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError(f"expected a uint8 HxW or HxWx3 image, got {t.dtype} {tuple(t.shape)}")
+        return t.to(device).contiguous()
+    return torch.from_numpy(FaceDetector._to_rgb(np.asarray(image))).to(device)
 
 
 def affine_from_3_points(src: np.ndarray, dst: np.ndarray) -> np.ndarray:
@@ -222,6 +260,14 @@ class FaceDetector:
         dets, counts = self.model.detect(frames, self.det_thresh, self.max_faces)
         return [self._faces(dets[f], min(int(counts[f]), self.max_faces)) for f in range(dets.shape[0])]
 
+    def detect_images(self, images) -> List[List[Dict]]:
+        """``detect`` for a sequence of images of different sizes (host arrays or device tensors, RGB
+        [H,W,3] or gray [H,W]) in one call -> per-image face lists.  The images run in input order in
+        chunks of ``max_frames``, each with its own letterbox geometry (``fr_detect_images``)."""
+        frames = [_device_frame(im, self.device) for im in images]
+        dets, counts = self.model.detect_images(frames, self.det_thresh, self.max_faces)
+        return [self._faces(dets[f], min(int(counts[f]), self.max_faces)) for f in range(len(frames))]
+
 
 class FaceProcessor:
     """detect -> align -> quality (face_recognition.py:160-216) with device alignment and blur."""
@@ -243,6 +289,68 @@ class FaceProcessor:
             raise ValueError(f"Could not load image: {image_path}")
         return self.process_numpy(image_rgb, return_all)
 
+    def process_images(self, images, return_all: bool = False, errors: str = "raise") -> List:
+        """``process_numpy`` / ``process_image`` for a sequence of images of different sizes -- arrays
+        (RGB [H,W,3] or gray [H,W]) or paths, mixed freely -- with the GPU work batched across the
+        sequence: one ``detect_images`` call (chunked by the detector's ``max_frames``), one
+        ``align_images`` launch over all faces of all images, one blur call over all crops.  Returns one
+        result list per item, each what ``process_numpy`` returns for that image (the same gate, sort
+        and dicts).  A detector without ``detect_images`` (a user-supplied ``detector=``) is asked
+        ``detect`` per image; alignment and blur are batched all the same.
+
+        An item that cannot be used -- a path that does not decode (``process_image``'s ValueError),
+        an array that is no HxW / HxWx3 image -- is reported as ``errors`` says: "raise" (default)
+        raises its ValueError before any GPU work, so nothing is half done; "return" puts the
+        ValueError instance in that item's slot of the returned list and processes the other items, so
+        one bad file does not lose the batch (``DatasetPreprocessor``).  JPEG parity as in
+        ``process_image``.
+
+        Against ``process_numpy`` per image: with a detector of fixed answers the results are equal bit
+        for bit.  With the GPU detector an image runs the same network in another batch, so its head
+        maps differ by fp32 rounding: the same faces, det_score within 1e-5 and boxes within 1 px where
+        scores are distinct.  On smooth content (a wall, a sky, a tiny image upscaled) neighbouring
+        anchors score equal to the last bits, and NMS may then keep a neighbouring box of the same
+        score in one path and not the other ("Mixed-size image batches")."""
+        if errors not in ("raise", "return"):
+            raise ValueError('errors must be "raise" or "return"')
+        out: List = [None] * len(images)
+        items = []  # (slot, the image as process_numpy would get it)
+        for slot, item in enumerate(images):
+            try:
+                if isinstance(item, (str, bytes)) or hasattr(item, "__fspath__"):
+                    image = load_image_rgb(item)
+                    if image is None:
+                        raise ValueError(f"Could not load image: {item}")
+                else:
+                    image = np.asarray(item)
+                    FaceDetector._to_rgb(image)  # the shape check of detect
+            except ValueError as e:
+                if errors == "raise":
+                    raise
+                out[slot] = e
+                continue
+            items.append((slot, image))
+        dev = self.aligner._ops.device
+        frames = [_device_frame(image, dev) for _slot, image in items]
+        if hasattr(self.detector, "detect_images"):
+            faces = self.detector.detect_images(frames) if frames else []
+        else:
+            faces = [self.detector.detect(image) for _slot, image in items]
+        crops = self.aligner.align_images(frames, [np.stack([f["landmarks"] for f in fs]) if fs else
+                                                   np.zeros((0, 5, 2), np.float32) for fs in faces])
+        blur = (self.quality_filter.compute_blur_scores(crops)
+                if self.quality_filter.check_blur and crops.shape[0] else None)
+        at = 0
+        for (slot, image), fs in zip(items, faces):
+            # to the host image by image: a block per image, as process_numpy's, not one block for the
+            # whole call (hundreds of MB for a chunk of group photographs, freshly paged in every call)
+            mine = crops[at:at + len(fs)].cpu().numpy()
+            if image.ndim == 2:  # a gray image's crops go back 2-D, as in process_numpy
+                mine = np.ascontiguousarray(mine[..., 0])
+            out[slot] = self._gate(fs, mine, None if blur is None else blur[at:at + len(fs)], return_all) if fs else []
+            at += len(fs)
+        return out
+
     def process_numpy(self, image_rgb: np.ndarray, return_all: bool = False) -> List[Dict]:
         faces = self.detector.detect(image_rgb)
         if len(faces) == 0:
@@ -258,6 +366,11 @@ class FaceProcessor:
         host = crops.cpu().numpy()
         if gray:
             host = np.ascontiguousarray(host[..., 0])
+        return self._gate(faces, host, blur, return_all)
+
+    def _gate(self, faces: List[Dict], host: np.ndarray, blur, return_all: bool) -> List[Dict]:
+        """The host gate, sort and result dicts of one image (face_recognition.py:192-216): ``host[i]``
+        the aligned crop and ``blur[i]`` the blur score (``blur`` None: not checked) of ``faces[i]``."""
         results = []
         for i, face in enumerate(faces):
             ok, q = self.quality_filter.is_valid(face, None, None if blur is None else float(blur[i]))

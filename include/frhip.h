@@ -376,6 +376,42 @@ int fr_blur_scores(fr_handle* h, const uint8_t* crops, int n, int height, int wi
 int fr_detect(fr_handle* h, const uint8_t* frames, int n, int height, int width, float det_thresh, int max_faces,
               float* dets, int32_t* counts, void* stream);
 
+/* fr_detect for n images of n different sizes (a folder of photographs): images: host array of n
+ * device pointers, image i uint8 [h_i][w_i][3] RGB; sizes: host int32 [n][2] = h_i, w_i, each side in
+ * [1, FR_IMAGE_MAX_SIDE].  Every image gets its own letterbox geometry (new_w, new_h, det_scale, resize
+ * tables and SIMD / scalar rounding split, as fr_detect computes them for that size): its canvas is
+ * bitwise fr_detect's canvas of that image alone, and decode divides by its own det_scale.  NMS, the
+ * layout of dets / counts (host; synchronises) and the 4096-anchor limit (FR_ERR_UNSUPPORTED; the
+ * message names the image) are fr_detect's.
+ *   Chunk rule (part of the contract: the conv kernels' fp32 rounding depends on the batch an image
+ *   runs in): images run in input order in chunks of the handle's max_frames, chunk c = images
+ *   [c * max_frames, min(n, (c + 1) * max_frames)).
+ *   Row-reduction rule: a chunk skips the letterbox's invariant bottom rows as fr_detect does, planned
+ *   for the largest new_h of the chunk (the canvas rows from there on are zeros in every image of the
+ *   chunk); a chunk that holds a portrait image therefore skips nothing.
+ *   A chunk whose images all have one size runs fr_detect's network launches on fr_detect's canvases:
+ *   its dets and counts are bitwise fr_detect's for the same frames.
+ * FR_ERR_INVALID_ARGUMENT, with the image's index in the message: a NULL pointer in images, a side
+ * outside [1, FR_IMAGE_MAX_SIDE], an image too small to letterbox (new_w < 1 or new_h < 1); also
+ * max_faces < 1 and NULL arrays.  Nothing runs when any image is refused.  n == 0 is a no-op. */
+#define FR_IMAGE_MAX_SIDE 8192
+int fr_detect_images(fr_handle* h, const uint8_t* const* images /* host [n] device pointers */,
+                     const int32_t* sizes /* host [n][2] = height, width */, int n, float det_thresh,
+                     int max_faces, float* dets /* host [n][max_faces][15] */, int32_t* counts /* host [n] */,
+                     void* stream);
+
+/* fr_align_faces for faces that come from different images: face j reads image face_image[j] (images /
+ * sizes as fr_detect_images takes them, any side >= 1; an image no face refers to is fine).  The
+ * similarity fit is fr_align_faces' (host, double), the warp its arithmetic (INTER_LINEAR,
+ * BORDER_CONSTANT 0): out[j] and tforms[j] are bitwise what fr_align_faces gives for that image and that
+ * face alone.  One launch and one staging copy for any n_faces.  Synchronises.  Any handle will do,
+ * finalised or not.  FR_ERR_INVALID_ARGUMENT: face_image[j] outside [0, n_images), NULL buffers or image
+ * pointers, a side < 1, out_size outside [1, 1024], a failed fit.  n_faces == 0 is a no-op. */
+int fr_align_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n_images,
+                    const float* landmarks /* host [n_faces][5][2] */, const int32_t* face_image /* host [n_faces] */,
+                    int n_faces, int out_size, uint8_t* out /* device [n_faces][S][S][3] */,
+                    double* tforms /* host [n_faces][2][3] or NULL */, void* stream);
+
 /* Conv arithmetic of this handle.  FR_PRECISION_F32 (default): exact f32 products and f32
  * accumulation on fp32 MFMA -- the parity path.  FR_PRECISION_BF16X3 (opt-in fast mode):
  * each f32 operand split into bf16 hi + lo, x.y ~= hi.hi + hi.lo + lo.hi on bf16 MFMA with f32

@@ -134,6 +134,12 @@ int frt_set_eval_chunk(int probes);
  * or NULL.  Synchronises. */
 int frt_detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int width, float* heads,
                          uint8_t* canvas, void* stream);
+/* The same for one chunk of fr_detect_images: n <= max_frames images of their own sizes (images /
+ * sizes as fr_detect_images takes them), run exactly as fr_detect_images runs that chunk: per-image
+ * letterbox, the chunk's row plan (none with row reduction switched off: the full canvas).  heads and
+ * canvas as above, canvas i the full 640-row canvas of image i.  Synchronises. */
+int frt_detector_forward_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* heads,
+                                uint8_t* canvas, void* stream);
 /* A/B: the stem and stage 1 skip the letterbox's invariant bottom rows (on, the default) or run
  * the full 640-row canvas (0).  Both compute the same network to fp32 rounding. */
 int frt_set_detector_row_reduction(fr_handle* h, int on);
