@@ -9,7 +9,8 @@ fallback.
 from .arch import block_specs, flop_per_face, state_dict_schema  # noqa: F401
 
 __all__ = ["FaceEmbedder", "GalleryManager", "FaceMatcher", "StudentEnrollment", "SimpleTracker", "FrameAccumulator",
-           "CameraFaceCapture", "LiveRecognitionTracker", "LiveFaceRecognition", "DatasetPreprocessor", "ProbeSegmenter", "block_specs", "flop_per_face", "state_dict_schema"]
+           "CameraFaceCapture", "LiveRecognitionTracker", "LiveFaceRecognition", "DatasetPreprocessor", "ProbeSegmenter",
+           "ProbeLabeler", "EmbeddingGenerator", "block_specs", "flop_per_face", "state_dict_schema"]
 
 
 def __getattr__(name):
@@ -37,4 +38,10 @@ def __getattr__(name):
     if name == "ProbeSegmenter":
         from .segment_dataset import ProbeSegmenter
         return ProbeSegmenter
+    if name == "ProbeLabeler":
+        from .probe_labeler import ProbeLabeler
+        return ProbeLabeler
+    if name == "EmbeddingGenerator":
+        from .embedding_generator import EmbeddingGenerator
+        return EmbeddingGenerator
     raise AttributeError(name)

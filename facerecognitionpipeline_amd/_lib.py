@@ -35,6 +35,8 @@ _SIGNATURES = {
     "fr_embed": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     "fr_embed_host": (_I, [_P, _P, _I, _I, _I, _P, _I]),
     "fr_resize_crops": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "fr_resize_images": (_I, [_P, _P, _P, _I, _P, _P]),
+    "fr_embed_images": (_I, [_P, _P, _P, _I, _P, _I, _P]),
     "fr_augment_faces": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "fr_gallery_set": (_I, [_P, _P, _I, _I, _I, _P]),
     "fr_gallery_size": (_I, [_P, ctypes.POINTER(_I)]),
@@ -508,6 +510,41 @@ class Handle:
                                         fi.ctypes.data, n, S, ptr(out) if n else None, tf.ctypes.data,
                                         stream_of(self.device)), self.h)
         return tf
+
+    def resize_images(self, images, out: torch.Tensor) -> None:
+        """``resize_crops`` for a list of uint8 [H,W,3] RGB device tensors of different sizes -> out uint8
+        [n,112,112,3] on the device, one launch per chunk of the handle's max_batch (include/frhip.h,
+        fr_resize_images)."""
+        kept, ptrs, sizes = self._image_list(images)
+        n = len(kept)
+        if (out.dtype != torch.uint8 or tuple(out.shape) != (n, 112, 112, 3) or out.device != self.device
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 {[n, 112, 112, 3]} tensor on {self.device}")
+        check(self._lib.fr_resize_images(self.h, ptrs.ctypes.data, sizes.ctypes.data, n, ptr(out) if n else None,
+                                         stream_of(self.device)), self.h)
+
+    def embed_images(self, images, out: torch.Tensor, normalize: bool = True) -> None:
+        """``embed`` for such a list -> out float32 [n,512] on the device, in fr_embed's chunks of
+        max_batch, each resized straight into the forward's input (fr_embed_images)."""
+        _kept, ptrs, sizes = self._image_list(images)
+        self.embed_image_ptrs(ptrs, sizes, out, normalize)
+
+    def embed_image_ptrs(self, ptrs, sizes, out: torch.Tensor, normalize: bool = True) -> None:
+        """``embed_images`` on the arrays the library takes: ``ptrs`` uint64 [n] device addresses of
+        uint8 [h_i, w_i, 3] images, ``sizes`` int32 [n,2] = h_i, w_i (a caller that packed many crops into
+        one allocation passes addresses inside it).  The images must stay allocated until the current
+        stream has run the call."""
+        import numpy as np
+        ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1, 2)
+        n = ptrs.shape[0]
+        if sizes.shape[0] != n:
+            raise ValueError(f"sizes names {sizes.shape[0]} images, ptrs {n}")
+        if (out.dtype != torch.float32 or tuple(out.shape) != (n, 512) or out.device != self.device
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 {[n, 512]} tensor on {self.device}")
+        check(self._lib.fr_embed_images(self.h, ptrs.ctypes.data, sizes.ctypes.data, n, ptr(out) if n else None,
+                                        int(normalize), stream_of(self.device)), self.h)
 
     def set_precision(self, mode: str) -> None:
         modes = {"fp32": 0, "f32": 0, "bf16x3": 1}

@@ -8,6 +8,8 @@
 //                      zero det_w x det_h canvas, in OpenCV's fixed point (11-bit
 //                      coefficients from the host; SSE2 vertical rounding for the
 //                      vectorised part of each row, scalar rounding for its tail)
+//   resize_images_kernel  the same resize for the embedder: crops of different sizes to
+//                      112 x 112 (fr_resize_images / fr_embed_images, embed_forward.cpp)
 //   det_stem_kernel    blobFromImage ((x - 127.5) / 128, RGB) fused into conv3x3 s2
 //                      3->C + BN + ReLU; det_stem_mfma_kernel the same on MFMA (K = 27 -> 28)
 //   maxpool3_kernel    MaxPool2d(3, 2, 1), NHWC
@@ -84,6 +86,28 @@ __global__ __launch_bounds__(256) void letterbox_images_kernel(const LetterboxIm
   const LetterboxImage im = imgs[f];
   reinterpret_cast<unsigned*>(out + (long long)f * dh * row)[e4] =
       letterbox_group(im.src, im.W, tabs + im.xtab, tabs + im.ytab, im.new_w, im.new_h, im.simd_end, row4, e4);
+}
+
+// The ragged crop form (fr_resize_images / fr_embed_images): image f of its own size resized to the
+// embedder's CROP_SIDE x CROP_SIDE x 3 input.  The output size and row4 = 84 are compile-time
+// constants, so letterbox_group's / row4 and / 3 fold to multiplies and, with new_w = new_h =
+// CROP_SIDE, its zero-fill tests fold away (e4 < CROP_GROUPS bounds y and x).  A CROP_SIDE-square
+// source whose address allows it is a straight 4-byte copy (copy: set by the host).
+constexpr int CROP_SIDE = 112, CROP_ROW4 = CROP_SIDE * 3 / 4, CROP_GROUPS = CROP_SIDE * CROP_ROW4;
+static_assert(CROP_SIDE * 3 % 4 == 0, "a crop row is whole 4-byte groups");
+__global__ __launch_bounds__(256) void resize_images_kernel(const CropImage* __restrict__ imgs,
+                                                            const int* __restrict__ tabs, int simd_end,
+                                                            uint8_t* __restrict__ out) {
+  const int f = blockIdx.y;
+  const int e4 = blockIdx.x * 256 + threadIdx.x;
+  if (e4 >= CROP_GROUPS) return;
+  const CropImage im = imgs[f];
+  unsigned* dst = reinterpret_cast<unsigned*>(out + (long long)f * (CROP_GROUPS * 4));
+  if (im.copy)
+    dst[e4] = reinterpret_cast<const unsigned*>(im.src)[e4];
+  else
+    dst[e4] = letterbox_group(im.src, im.W, tabs + im.xtab, tabs + im.ytab, CROP_SIDE, CROP_SIDE, simd_end,
+                              CROP_ROW4, e4);
 }
 
 // One block per (frame, output row); thread t: channel group t & 3 (8 channels), pixels (t >> 2) + 64 j.
@@ -371,6 +395,15 @@ hipError_t launch_letterbox_images(const LetterboxImage* imgs, const int* tabs, 
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(letterbox_images_kernel, dim3((unsigned)((elems / 4 + 255) / 256), n), dim3(256), 0, s, imgs,
                      tabs, dw, dh, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_resize_images(const CropImage* imgs, const int* tabs, int n, int simd_end, uint8_t* out,
+                                hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > 65535 || (reinterpret_cast<uintptr_t>(out) & 3)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(resize_images_kernel, dim3((CROP_GROUPS + 255) / 256, n), dim3(256), 0, s, imgs, tabs, simd_end,
+                     out);
   return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 //   FaceEmbedder.extract_embeddings_batch   face_embedder.py:137-182 (A3)
 //   GalleryManager.search                   gallery_manager.py:189-205 (A11)
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -431,6 +432,101 @@ int embed_any(fr_handle* h, const uint8_t* rgb, int n, int height, int width, fl
     if (rc) return rc;
     rc = embed_device(h, h->rs_stage, bn, out + (size_t)off * 512, normalize, s);
     if (rc) return rc;
+  }
+  return FR_OK;
+}
+
+int check_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n) {
+  for (int i = 0; i < n; ++i) {
+    const int height = sizes[2 * i], width = sizes[2 * i + 1];
+    if (!images[i]) return fail(h, FR_ERR_INVALID_ARGUMENT, "image " + std::to_string(i) + " is NULL");
+    if (height < 1 || height > FR_IMAGE_MAX_SIDE || width < 1 || width > FR_IMAGE_MAX_SIDE)
+      return fail(h, FR_ERR_INVALID_ARGUMENT,
+                  "image " + std::to_string(i) + " is " + std::to_string(height) + " x " + std::to_string(width) +
+                      " (each side must be in [1, " + std::to_string(FR_IMAGE_MAX_SIDE) + "])");
+  }
+  return FR_OK;
+}
+
+// The ragged resize (fr_resize_images / fr_embed_images; images validated by check_images), in chunks
+// of max_batch.  stage_images lays every chunk's staging out in h->ri_host, chunk c at ri_chunks[c]:
+//   [bn] CropImage | coefficient tables, [112 x][4] then [112 y][4] per distinct size of the chunk
+// (resize_device's tables, built once per size, not per image; 112 x 112 images that the kernel
+// copies need none).  One host buffer holds all chunks of a call, so no chunk's pageable bytes are
+// rewritten while its copy may be pending; an earlier call's copies are waited for at entry.
+// resize_images_chunk then makes chunk c's one copy and one launch.
+int stage_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, hipStream_t s) {
+  FR_HIP(h, hipStreamSynchronize(s));
+  constexpr size_t TAB_INTS = 4 * (112 + 112);
+  h->ri_host.clear();
+  h->ri_chunks.clear();
+  std::vector<int> sized;  // (H, W, table offset) of the chunk's distinct sizes
+  size_t largest = 0;
+  for (int off = 0; off < n; off += h->max_batch) {
+    const int bn = std::min(h->max_batch, n - off);
+    const size_t at = h->ri_host.size(), tab_off = (size_t)bn * sizeof(CropImage);
+    h->ri_chunks.push_back(at);
+    h->ri_host.resize(at + tab_off);
+    sized.clear();
+    for (int i = 0; i < bn; ++i) {
+      const int H = sizes[2 * (off + i)], W = sizes[2 * (off + i) + 1];
+      const uint8_t* src = images[off + i];
+      CropImage im{src, W, 0, 0, H == 112 && W == 112 && (reinterpret_cast<uintptr_t>(src) & 3) == 0};
+      if (!im.copy) {
+        int t = -1;
+        for (size_t k = 0; k < sized.size(); k += 3)
+          if (sized[k] == H && sized[k + 1] == W) t = sized[k + 2];
+        if (t < 0) {
+          t = (int)(sized.size() / 3 * TAB_INTS);
+          sized.insert(sized.end(), {H, W, t});
+          h->ri_host.resize(at + tab_off + (t + TAB_INTS) * sizeof(int));
+          int* tab = reinterpret_cast<int*>(h->ri_host.data() + at + tab_off) + t;
+          resize_axis_table(112, W, tab);
+          resize_axis_table(112, H, tab + 4 * 112);
+        }
+        im.xtab = t;
+        im.ytab = t + 4 * 112;
+      }
+      memcpy(h->ri_host.data() + at + (size_t)i * sizeof(CropImage), &im, sizeof(im));
+    }
+    h->ri_host.resize((h->ri_host.size() + 15) & ~size_t(15));
+    largest = std::max(largest, h->ri_host.size() - at);
+  }
+  return ensure_buf(h, &h->ri_dev, &h->ri_dev_cap, largest);
+}
+
+int resize_images_chunk(fr_handle* h, size_t c, int bn, uint8_t* dst, hipStream_t s) {
+  const size_t at = h->ri_chunks[c];
+  const size_t bytes = (c + 1 < h->ri_chunks.size() ? h->ri_chunks[c + 1] : h->ri_host.size()) - at;
+  // (stream order on s keeps the copy behind the previous chunk's launch, which reads ri_dev)
+  FR_HIP(h, hipMemcpyAsync(h->ri_dev, h->ri_host.data() + at, bytes, hipMemcpyHostToDevice, s));
+  const char* base = static_cast<const char*>(h->ri_dev);
+  ProfScope ps(h, s, 0.0, 0);
+  const hipError_t e = launch_resize_images(reinterpret_cast<const CropImage*>(base),
+                                            reinterpret_cast<const int*>(base + (size_t)bn * sizeof(CropImage)), bn,
+                                            resize_simd_end(112 * 3), dst, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("resize launch: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int resize_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, uint8_t* dst,
+                  hipStream_t s) {
+  if (int rc = stage_images(h, images, sizes, n, s)) return rc;
+  for (size_t c = 0; c < h->ri_chunks.size(); ++c) {
+    const int off = (int)c * h->max_batch, bn = std::min(h->max_batch, n - off);
+    if (int rc = resize_images_chunk(h, c, bn, dst + (size_t)off * 112 * 112 * 3, s)) return rc;
+  }
+  return FR_OK;
+}
+
+// embed_any for such a list: each chunk resized into rs_stage, then through embed_device.
+int embed_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* out, int normalize,
+                 hipStream_t s) {
+  if (int rc = stage_images(h, images, sizes, n, s)) return rc;
+  for (size_t c = 0; c < h->ri_chunks.size(); ++c) {
+    const int off = (int)c * h->max_batch, bn = std::min(h->max_batch, n - off);
+    if (int rc = resize_images_chunk(h, c, bn, h->rs_stage, s)) return rc;
+    if (int rc = embed_device(h, h->rs_stage, bn, out + (size_t)off * 512, normalize, s)) return rc;
   }
   return FR_OK;
 }

@@ -363,6 +363,16 @@ struct LetterboxImage {
 };
 hipError_t launch_letterbox_images(const LetterboxImage* imgs, const int* tabs, int n, int dw, int dh, uint8_t* out,
                                    hipStream_t s);
+// cv2.resize INTER_LINEAR of n images of different sizes (n <= 65535) to 112 x 112 x 3 each (out:
+// [n][112][112][3], 4-byte aligned): image f's tables at tabs + xtab / ytab ([112][4] each).
+struct CropImage {
+  const uint8_t* src;  // device uint8 [H][W][3]
+  int W;
+  int xtab, ytab;  // offsets into tabs, in ints
+  int copy;        // the image is 112 x 112 at a 4-byte aligned address: copied, its tables unused
+};
+hipError_t launch_resize_images(const CropImage* imgs, const int* tabs, int n, int simd_end, uint8_t* out,
+                                hipStream_t s);
 // (x - 127.5)/128 -> conv3x3 s2 p1 3->C (C % 8 == 0, <= 32; weights [27][C]) -> BN -> ReLU, NHWC.
 hipError_t launch_det_stem(const uint8_t* img, int n, int H, int W, int C, const float* w27xC, const float* scale,
                            const float* shift, float* y, hipStream_t s);

@@ -116,6 +116,33 @@ int fr_resize_crops(fr_handle* h, const uint8_t* src, int n, int height, int wid
   return resize_device(h, src, n, height, width, dst, (hipStream_t)stream);
 }
 
+int fr_resize_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, uint8_t* dst,
+                     void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (n < 0 || (n > 0 && (!images || !sizes || !dst)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or NULL images / sizes / dst");
+  if (n == 0) return FR_OK;
+  if (int rc = check_images(h, images, sizes, n)) return rc;
+  DeviceGuard dg(h->device);
+  return resize_images(h, images, sizes, n, dst, (hipStream_t)stream);
+}
+
+int fr_embed_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* out,
+                    int normalize, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->detector) return fail(h, FR_ERR_STATE, "this handle is a detector (scrfd_10g); use fr_detect");
+  if (!h->finalized) return fail(h, FR_ERR_STATE, "model not finalised (fr_finalize)");
+  if (n < 0 || (n > 0 && (!images || !sizes || !out)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or NULL images / sizes / out");
+  if (n == 0) return FR_OK;
+  if (int rc = check_images(h, images, sizes, n)) return rc;
+  if (int rc = check_dev_err(h)) return rc;  // reported by earlier asynchronous work
+  DeviceGuard dg(h->device);
+  return embed_images(h, images, sizes, n, out, normalize, (hipStream_t)stream);
+}
+
 int fr_augment_faces(fr_handle* h, const uint8_t* crops, int n, int height, int width, int num_augmentations,
                      uint8_t* out, void* stream) {
   if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");

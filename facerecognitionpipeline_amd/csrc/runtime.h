@@ -170,6 +170,12 @@ struct fr_handle {
   uint8_t* rs_stage = nullptr;
   void* rs_src = nullptr;
   size_t rs_src_cap = 0;
+  // fr_resize_images / fr_embed_images: the host staging of every chunk of one call (descriptors +
+  // tables; chunk c starts at ri_chunks[c]) and the device copy of the chunk in flight
+  std::vector<char> ri_host;
+  std::vector<size_t> ri_chunks;
+  void* ri_dev = nullptr;
+  size_t ri_dev_cap = 0;
 
   // gallery + match workspace
   float* gallery = nullptr;
@@ -298,6 +304,7 @@ struct fr_handle {
     }
     (void)hipFree(rs_stage);
     (void)hipFree(rs_src);
+    (void)hipFree(ri_dev);
     (void)hipFree(gallery);
     (void)hipFree(qn);
     (void)hipFree(scores);
@@ -436,6 +443,13 @@ int resize_device(fr_handle* h, const uint8_t* src, int n, int H, int W, uint8_t
 int check_crop_size(fr_handle* h, int height, int width);
 int embed_any(fr_handle* h, const uint8_t* rgb, int n, int height, int width, float* out, int normalize,
               hipStream_t s);
+// fr_resize_images / fr_embed_images: check_images refuses a NULL image or a side out of range
+// (naming the image); the other two run a checked list (and synchronise s at entry)
+int check_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n);
+int resize_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, uint8_t* dst,
+                  hipStream_t s);
+int embed_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* out, int normalize,
+                 hipStream_t s);
 int match_device(fr_handle* h, const float* Q, int n, int k, int32_t* idx, float* score, hipStream_t s);
 // Grow the gallery allocation to hold `rows` rows, keeping the first G rows (stream-ordered).
 int gallery_reserve(fr_handle* h, int rows, hipStream_t s);

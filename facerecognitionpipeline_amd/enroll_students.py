@@ -68,6 +68,33 @@ def augment_face_for_enrollment(face_image: np.ndarray, num_augmentations: int =
     return [out[v] for v in range(count)]
 
 
+def embed_augmented(embedder, handle: "_lib.Handle", device, faces: Sequence[np.ndarray],
+                    augmentation_per_face: int) -> np.ndarray:
+    """``augmentation_per_face`` copies of every crop of ``faces`` (HxWx3 uint8, any mix of sizes), made
+    on ``handle`` and embedded by ``embedder`` with ``normalize=True`` -> host float32
+    [len(faces) * A, 512], face-major and variant-minor.  One upload and one ``augment_faces`` launch per
+    crop size; the forward runs in ``max_batch`` chunks.  (``StudentEnrollment`` and
+    ``EmbeddingGenerator`` share it.)"""
+    A = augmentation_per_face
+    dev = torch.device(device)
+    emb = torch.empty((len(faces), A, 512), dtype=torch.float32, device=dev)
+    by_size: Dict[Tuple[int, int], List[int]] = {}
+    for i, f in enumerate(faces):
+        f = np.asarray(f)
+        if f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8:
+            raise ValueError(f"expected HxWx3 uint8 aligned crops, got {f.dtype} {f.shape}")
+        by_size.setdefault(f.shape[:2], []).append(i)
+    chunk = max(1, int(getattr(embedder, "max_batch", 256)))
+    for (H, W), rows in by_size.items():
+        crops = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(faces[i]) for i in rows]))).to(dev)
+        aug = handle.augment_faces(crops, A).reshape(len(rows) * A, H, W, 3)
+        gemb = torch.empty((len(rows) * A, 512), dtype=torch.float32, device=dev)
+        for off in range(0, len(aug), chunk):
+            embedder.embed_tensor(aug[off:off + chunk], normalize=True, out=gemb[off:off + chunk])
+        emb[torch.as_tensor(rows, device=dev)] = gemb.reshape(len(rows), A, 512)
+    return emb.reshape(len(faces) * A, 512).cpu().numpy()
+
+
 class StudentEnrollment:
     def __init__(self, gallery_path=PROJECT_ROOT / "gallery" / "students.pkl", min_faces_per_student=3,
                  max_faces_per_student=5, limit_images=0, image_indices=None, model_type="adaface",
@@ -157,25 +184,7 @@ class StudentEnrollment:
         sizes), embedded with ``normalize=True`` -> host float32 [len(faces) * A, 512], face-major
         and variant-minor (the reference's ``all_face_images`` order, :212-222).  One upload and
         one ``augment_faces`` launch per crop size; the forward runs in ``max_batch`` chunks."""
-        A = augmentation_per_face
-        dev = self.device
-        h = self._ops_handle()
-        emb = torch.empty((len(faces), A, 512), dtype=torch.float32, device=dev)
-        by_size: Dict[Tuple[int, int], List[int]] = {}
-        for i, f in enumerate(faces):
-            f = np.asarray(f)
-            if f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8:
-                raise ValueError(f"expected HxWx3 uint8 aligned crops, got {f.dtype} {f.shape}")
-            by_size.setdefault(f.shape[:2], []).append(i)
-        chunk = max(1, int(getattr(self.embedder, "max_batch", 256)))
-        for (H, W), rows in by_size.items():
-            crops = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(faces[i]) for i in rows]))).to(dev)
-            aug = h.augment_faces(crops, A).reshape(len(rows) * A, H, W, 3)
-            gemb = torch.empty((len(rows) * A, 512), dtype=torch.float32, device=dev)
-            for off in range(0, len(aug), chunk):
-                self.embedder.embed_tensor(aug[off:off + chunk], normalize=True, out=gemb[off:off + chunk])
-            emb[torch.as_tensor(rows, device=dev)] = gemb.reshape(len(rows), A, 512)
-        return emb.reshape(len(faces) * A, 512).cpu().numpy()
+        return embed_augmented(self.embedder, self._ops_handle(), self.device, faces, augmentation_per_face)
 
     def enroll_aligned(self, students: Sequence[Tuple], augmentation_per_face: int = 8) -> List[Tuple[bool, Dict]]:
         """Enroll many students from their aligned crops in one pass.  ``students``: (student_id,

@@ -593,3 +593,67 @@ def evaluate_segmented_comprehensive(gallery_embeddings, probe_positive, probe_n
         out[segment] = {"identification": _identification(pos, thresholds, aggregation, keep_identity_scores),
                         "verification": ver}
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# reading EmbeddingGenerator's files back (the notebook's load_embeddings / load_all_embeddings)
+# ---------------------------------------------------------------------------------------------
+EMBEDDING_FILES = {
+    "gallery_oneshot_base": "gallery_one-shot_base.pkl",
+    "gallery_oneshot_augmented": "gallery_one-shot_augmented.pkl",
+    "gallery_fewshot_base": "gallery_few-shot_base.pkl",
+    "gallery_fewshot_augmented": "gallery_few-shot_augmented.pkl",
+    "probe_positive_unsegmented": "probe_positive_unsegmented.pkl",
+    "probe_positive_segmented": "probe_positive_segmented.pkl",
+    "probe_negative": "probe_negative.pkl",
+}
+
+
+def load_embedding_pickle(path):
+    """``pickle.load`` of one of ``EmbeddingGenerator``'s files -- dicts, lists, str, int, bool and
+    numpy arrays -- through the gallery's whitelist unpickler cut down to numpy's reconstruction
+    globals: a pickle that names anything else raises ``pickle.UnpicklingError`` and runs nothing."""
+    import pickle
+    from .gallery_manager import _NUMPY_GLOBALS, _GalleryUnpickler
+
+    class _EmbeddingUnpickler(_GalleryUnpickler):
+        def find_class(self, module, name):
+            if (module, name) not in _NUMPY_GLOBALS:
+                raise pickle.UnpicklingError(f"embedding pickle names a global outside the whitelist: {module}.{name}")
+            return super().find_class(module, name)
+
+    with open(path, "rb") as f:
+        return _EmbeddingUnpickler(f).load()
+
+
+def load_embeddings(model_name: str, embeddings_root) -> Dict:
+    """The notebook's ``load_embeddings`` (``embeddings_root`` is a global there): the seven files of
+    ``<embeddings_root>/<model_name>`` under the notebook's keys, ``None`` for a file that is missing;
+    ``FileNotFoundError`` when the model directory is."""
+    from pathlib import Path
+    model_dir = Path(embeddings_root) / model_name
+    if not model_dir.exists():
+        raise FileNotFoundError(f"Model directory not found: {model_dir}")
+    return {key: load_embedding_pickle(model_dir / filename) if (model_dir / filename).exists() else None
+            for key, filename in EMBEDDING_FILES.items()}
+
+
+def load_all_embeddings(base_dir) -> Dict[str, Dict]:
+    """The notebook's ``load_all_embeddings``: every sub-directory of ``base_dir`` is a model, every
+    known ``.pkl`` in it a key; an unknown ``.pkl`` is warned about and skipped, a missing one has no key."""
+    from pathlib import Path
+    mapping = {filename: key for key, filename in EMBEDDING_FILES.items()}
+    all_embeddings: Dict[str, Dict] = {}
+    for model_dir in sorted(Path(base_dir).iterdir()):
+        if not model_dir.is_dir():
+            continue
+        all_embeddings[model_dir.name] = {}
+        for file in sorted(model_dir.iterdir()):
+            if file.suffix != ".pkl":
+                continue
+            key = mapping.get(file.name)
+            if key is None:
+                print(f"Warning: Unrecognized file {file.name}, skipping…")
+                continue
+            all_embeddings[model_dir.name][key] = load_embedding_pickle(file)
+    return all_embeddings

@@ -51,6 +51,9 @@ def _as_device(device) -> torch.device:
 
 
 class FaceEmbedder:
+    # embed_images packs host crops into upload buffers of about this size
+    upload_piece_bytes = 32 << 20
+
     def __init__(self, architecture: str = "ir_101", model_path: Optional[str] = None,
                  model_type: str = "adaface", device=None, max_batch: int = 256,
                  state_dict=None, weight_seed: Optional[int] = None, precision: str = "fp32",
@@ -189,6 +192,44 @@ class FaceEmbedder:
         if out is None:
             out = torch.empty((rgb.shape[0], 512), dtype=torch.float32, device=self.device)
         self.model.embed(rgb, out, normalize)
+        return out
+
+    def embed_images(self, images, normalize: bool = True) -> torch.Tensor:
+        """A list of HxWx3 uint8 RGB crops of any sizes (host arrays or device tensors, mixed freely)
+        -> float32 [n,512] on the device, in one library call (``fr_embed_images``): chunks of
+        ``max_batch`` in input order, each resized on the device straight into the forward's input.
+        The host arrays of the list are packed end to end and go up in pieces of about
+        ``upload_piece_bytes`` (the checks of ``extract_embeddings_batch`` apply to them); the library
+        gets their addresses inside the pieces."""
+        n = len(images)
+        ptrs = np.zeros(n, dtype=np.uint64)
+        sizes = np.zeros((n, 2), dtype=np.int32)
+        keep, rows, flats = [], [], []  # device tensors the call reads; host crops' rows and bytes
+        for i, f in enumerate(images):
+            self._check_shape(f)
+            sizes[i] = f.shape[:2]
+            if isinstance(f, torch.Tensor):
+                if f.dtype != torch.uint8:
+                    raise ValueError(f"device crops must be uint8, got {f.dtype}")
+                keep.append(f.to(self.device).contiguous())
+                ptrs[i] = keep[-1].data_ptr()
+            else:
+                rows.append(i)
+                flats.append(self._as_u8(f).reshape(-1))
+        start = 0
+        while start < len(flats):  # pieces of about upload_piece_bytes, each one concatenation and one upload
+            end, nbytes = start + 1, flats[start].size
+            while end < len(flats) and nbytes + flats[end].size <= self.upload_piece_bytes:
+                nbytes += flats[end].size
+                end += 1
+            offsets = np.zeros(end - start, dtype=np.int64)
+            np.cumsum([a.size for a in flats[start:end - 1]], out=offsets[1:])
+            keep.append(torch.from_numpy(np.concatenate(flats[start:end])).to(self.device))
+            ptrs[rows[start:end]] = (keep[-1].data_ptr() + offsets).astype(np.uint64)
+            start = end
+        out = torch.empty((n, 512), dtype=torch.float32, device=self.device)
+        # (`keep` may die with this frame: the allocator hands its memory out again in stream order)
+        self.model.embed_image_ptrs(ptrs, sizes, out, normalize)
         return out
 
     def _check_shape(self, face_image: np.ndarray) -> None:

@@ -412,6 +412,28 @@ int fr_align_images(fr_handle* h, const uint8_t* const* images, const int32_t* s
                     int n_faces, int out_size, uint8_t* out /* device [n_faces][S][S][3] */,
                     double* tforms /* host [n_faces][2][3] or NULL */, void* stream);
 
+/* fr_resize_crops for n crops of n different sizes (a folder of probe crops): images / sizes as
+ * fr_detect_images takes them.  dst[i] = cv2.resize(image i, (112, 112), INTER_LINEAR), bitwise what
+ * fr_resize_crops gives for image i alone at its size; a 112 x 112 image comes through byte for byte.
+ * Images run in input order in chunks of the handle's max_batch: one staging copy (the chunk's
+ * descriptors and its coefficient tables, built once per distinct size of the chunk) and one launch
+ * per chunk.  Any handle will do, finalised or not.  Synchronises `stream` at entry (the host
+ * staging of an earlier call may still be read by a pending copy) and is asynchronous on it after
+ * that: the images must stay alive until the stream reaches the end of the call's work.
+ * FR_ERR_INVALID_ARGUMENT, with the image's index in the message: a NULL pointer in images, a side
+ * outside [1, FR_IMAGE_MAX_SIDE]; also NULL arrays.  Nothing runs when any image is refused.
+ * n == 0 is a no-op. */
+int fr_resize_images(fr_handle* h, const uint8_t* const* images /* host [n] device pointers */,
+                     const int32_t* sizes /* host [n][2] = height, width */, int n,
+                     uint8_t* dst /* device [n][112][112][3] */, void* stream);
+/* fr_embed for the same kind of list: chunk c = images [c * max_batch, min(n, (c + 1) * max_batch))
+ * (fr_embed's chunk boundaries) is resized straight into the forward's input and embedded, so out is
+ * bitwise fr_embed(h, dst, n, 112, 112, out, normalize, stream) on fr_resize_images' dst.
+ * Synchronises as fr_resize_images does; its errors, and fr_embed's FR_ERR_STATE on a handle that is
+ * not a finalised embedder. */
+int fr_embed_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n,
+                    float* out /* device [n][512] */, int normalize, void* stream);
+
 /* Conv arithmetic of this handle.  FR_PRECISION_F32 (default): exact f32 products and f32
  * accumulation on fp32 MFMA -- the parity path.  FR_PRECISION_BF16X3 (opt-in fast mode):
  * each f32 operand split into bf16 hi + lo, x.y ~= hi.hi + hi.lo + lo.hi on bf16 MFMA with f32
