@@ -10,7 +10,8 @@ from .arch import block_specs, flop_per_face, state_dict_schema  # noqa: F401
 
 __all__ = ["FaceEmbedder", "GalleryManager", "FaceMatcher", "StudentEnrollment", "SimpleTracker", "FrameAccumulator",
            "CameraFaceCapture", "LiveRecognitionTracker", "LiveFaceRecognition", "DatasetPreprocessor", "ProbeSegmenter",
-           "ProbeLabeler", "EmbeddingGenerator", "block_specs", "flop_per_face", "state_dict_schema"]
+           "ProbeLabeler", "EmbeddingGenerator", "FaceRecognitionServer", "ServerRecognitionTracker", "create_app",
+           "block_specs", "flop_per_face", "state_dict_schema"]
 
 
 def __getattr__(name):
@@ -44,4 +45,10 @@ def __getattr__(name):
     if name == "EmbeddingGenerator":
         from .embedding_generator import EmbeddingGenerator
         return EmbeddingGenerator
+    if name in ("FaceRecognitionServer", "create_app"):
+        from . import face_recognition_server
+        return getattr(face_recognition_server, name)
+    if name == "ServerRecognitionTracker":  # the server module's LiveRecognitionTracker: the name is the live loop's here
+        from .face_recognition_server import LiveRecognitionTracker
+        return LiveRecognitionTracker
     raise AttributeError(name)

@@ -48,6 +48,8 @@ _SIGNATURES = {
     "fr_capture_tracks": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_double, _I, ctypes.c_double, _I, _P, _P, _P,
                                _P, _P]),
     "fr_live_tracks": (_I, [_P, _P, _P, _P, _P, _I, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "fr_server_tracks": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P,
+                              _P]),
     "fr_identity_scores": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "fr_eval_probes": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "fr_match_topk": (_I, [_P, _P, _I, _I, _P, _P, _P]),
@@ -364,6 +366,40 @@ class Handle:
         if rc != FR_ERR_UNSUPPORTED or raise_on_clip_error:
             check(rc, self.h)
         return track_id, prev, attempt, best, info
+
+    def server_tracks(self, metrics: torch.Tensor, clock: torch.Tensor, order: torch.Tensor, track_offsets,
+                      max_attempts: int = 3, buffer_size: int = 10, retry_cooldown: float = 10.0,
+                      det_gate: float = 0.6, raise_on_track_error: bool = True):
+        """The gating, the retry cooldown and the frame selection of the server's
+        ``LiveRecognitionTracker`` (face_recognition_server.py:23-124) for every track of a recorded
+        request log in one launch.  ``metrics`` float64 [n,2] (det_score, blur_score), ``clock``
+        float64 [n] (the request's clock, repeated for its faces) and ``order`` int32 [n] (detection
+        indices grouped by track, arrival order within a track) on the device; track t =
+        ``order[track_offsets[t]:track_offsets[t+1]]`` -> (attempt int32 [n], best int32 [n], state
+        int32 [n] of ``FR_SERVER_*``, track_info int32 [T,4] = attempts, cooldowns set, resets, error)
+        on the device.  A track with a non-finite value or a bad ``order`` entry raises
+        NotImplementedError; with ``raise_on_track_error=False`` the outputs are returned instead and
+        ``track_info[:, 3]`` names the tracks (-1 / -1 / ``FR_SERVER_GATED`` throughout)."""
+        if (metrics.dim() != 2 or metrics.shape[1] != 2 or metrics.dtype != torch.float64
+                or clock.dtype != torch.float64 or tuple(clock.shape) != (metrics.shape[0],)
+                or order.dtype != torch.int32 or order.dim() != 1):
+            raise ValueError("expected metrics float64 [n,2], clock float64 [n] and order int32 [total]")
+        for name, x in (("metrics", metrics), ("clock", clock), ("order", order)):
+            self._require_device(name, x)
+        off, T = _csr_offsets(track_offsets)
+        if T < 0 or int(off[-1]) != order.shape[0]:
+            raise ValueError(f"track_offsets must end at the {order.shape[0]} entries of order")
+        metrics, clock, order = metrics.contiguous(), clock.contiguous(), order.contiguous()
+        n = metrics.shape[0]
+        attempt, best = (torch.full((n,), -1, dtype=torch.int32, device=self.device) for _ in range(2))
+        state = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        info = torch.empty((T, 4), dtype=torch.int32, device=self.device)
+        rc = self._lib.fr_server_tracks(self.h, ptr(metrics), ptr(clock), ptr(order), off.ctypes.data, T, n,
+                                        int(max_attempts), int(buffer_size), float(retry_cooldown), float(det_gate),
+                                        ptr(attempt), ptr(best), ptr(state), ptr(info), stream_of(self.device))
+        if rc != FR_ERR_UNSUPPORTED or raise_on_track_error:
+            check(rc, self.h)
+        return attempt, best, state, info
 
     AGGREGATIONS = {"max": 0, "mean": 1, "topk": 2}
 

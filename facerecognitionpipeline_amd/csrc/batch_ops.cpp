@@ -1,5 +1,6 @@
 // libfrhip public C API (include/frhip.h), the calls over CSR batches: fr_build_templates,
-// fr_track_consensus, fr_capture_tracks, fr_live_tracks, fr_identity_scores and fr_eval_probes.
+// fr_track_consensus, fr_capture_tracks, fr_live_tracks, fr_server_tracks, fr_identity_scores and
+// fr_eval_probes.
 // They share one shape: lock_handle; the argument checks, which need no handle and so report the
 // same way for h == NULL (csr_check for the offsets); "NULL handle"; the offsets staged with
 // stage_int32; the launch; one stream synchronise, because the staging read pageable host memory.
@@ -172,6 +173,51 @@ int fr_live_tracks(fr_handle* h, const int32_t* bbox, const double* metrics, con
     if (info[(size_t)c * 4 + 3])
       return fail(h, FR_ERR_UNSUPPORTED,
                   "clip " + std::to_string(c) + ": a box coordinate beyond +-" + std::to_string(CAPTURE_COORD_MAX));
+  return FR_OK;
+}
+
+int fr_server_tracks(fr_handle* h, const double* metrics, const double* clock, const int32_t* order,
+                     const int32_t* track_offsets, int n_tracks, int n_dets, int max_attempts, int buffer_size,
+                     double retry_cooldown, double det_gate, int32_t* attempt, int32_t* best, int32_t* state,
+                     int32_t* track_info, void* stream) {
+  auto lk = lock_handle(h);
+  if (n_tracks < 0 || n_dets < 0) return fail(h, FR_ERR_INVALID_ARGUMENT, "n_tracks and n_dets must be >= 0");
+  if (max_attempts < 1 || max_attempts > SERVER_MAX_ATTEMPTS)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "max_attempts must be in [1, " + std::to_string(SERVER_MAX_ATTEMPTS) + "]");
+  if (buffer_size < 1 || buffer_size > SERVER_MAX_BUFFER)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "buffer_size must be in [1, " + std::to_string(SERVER_MAX_BUFFER) + "]");
+  if (!std::isfinite(retry_cooldown) || retry_cooldown < 0.0)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "retry_cooldown must be finite and >= 0");
+  if (!std::isfinite(det_gate)) return fail(h, FR_ERR_INVALID_ARGUMENT, "det_gate must be finite");
+  if (n_tracks > 0) {
+    if (!track_offsets) return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer (offsets)");
+    // tracks of any number of appearances, also none
+    const std::string bad = csr_check(track_offsets, n_tracks, 0, INT32_MAX, {"track_offsets", "track", "appearances"});
+    if (!bad.empty()) return fail(h, FR_ERR_INVALID_ARGUMENT, bad);
+    const int total = track_offsets[n_tracks];
+    if (!track_info || (total > 0 && (!metrics || !clock || !order || !attempt || !best || !state)))
+      return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer");
+  }
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  if (n_tracks == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int* d_off;
+  if (int rc = stage_int32(h, s, {{track_offsets, (size_t)n_tracks + 1}}, &d_off)) return rc;
+  const hipError_t e = launch_server_tracks(metrics, clock, order, d_off, n_tracks, n_dets, max_attempts, buffer_size,
+                                            retry_cooldown, det_gate, attempt, best, state, track_info, s);
+  if (e != hipSuccess) return launch_fail(h, "server tracks", e);
+  std::vector<int32_t> info((size_t)n_tracks * 4);
+  FR_HIP(h, hipMemcpyAsync(info.data(), track_info, info.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
+  for (int t = 0; t < n_tracks; ++t) {
+    const int err = info[(size_t)t * 4 + 3];
+    if (err)
+      return fail(h, FR_ERR_UNSUPPORTED,
+                  "track " + std::to_string(t) +
+                      (err & SERVER_ERR_ORDER ? ": an order entry outside [0, " + std::to_string(n_dets) + ")"
+                                              : ": a non-finite metric or clock"));
+  }
   return FR_OK;
 }
 

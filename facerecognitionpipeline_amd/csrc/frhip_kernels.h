@@ -313,6 +313,22 @@ hipError_t launch_live_tracks(const int* bbox, const double* metrics, const int*
                               int buffer_size, int* track_id, int* prev, int* attempt, int* best, int* clip_info,
                               hipStream_t s);
 
+// Server sessions (server.hip: the server's LiveRecognitionTracker) of n_tracks CSR slices of `order`
+// [track_off[n_tracks]], detection indices into metrics [n_dets][2] = det_score, blur_score and clock
+// [n_dets] (seconds), a track's appearances in arrival order; track_off on the device.  attempt
+// (ordinal among the track's attempts) / best (detection index) / state (SERVER_*): [n_dets], -1 for
+// none; track_info: [n_tracks][4] = attempts, cooldowns set, resets, SERVER_ERR_* (0: none).
+constexpr int SERVER_MAX_ATTEMPTS = 16;
+constexpr int SERVER_MAX_BUFFER = 64;
+enum ServerState : int {
+  SERVER_GATED = 0, SERVER_ATTEMPT = 1, SERVER_COOLDOWN = 2, SERVER_COOLDOWN_SET = 3, SERVER_RESET = 4
+};
+enum ServerError : int { SERVER_ERR_VALUE = 1, SERVER_ERR_ORDER = 2 };  // a bit each
+hipError_t launch_server_tracks(const double* metrics, const double* clock, const int* order, const int* track_off,
+                                int n_tracks, int n_dets, int max_attempts, int buffer_size, double retry_cooldown,
+                                double det_gate, int* attempt, int* best, int* state, int* track_info,
+                                hipStream_t s);
+
 // Model evaluation (evaluate.hip: the notebook's cosine_similarity / aggregate_* / identify_probe /
 // compute_rank_metrics and the threshold loops of evaluate_*_comprehensive).
 constexpr int EVAL_MAX_ROWS = 1024;      // gallery rows of one identity

@@ -16,6 +16,8 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
                                                               30, 80.0, 12, 0.5, False)  # [N] x 3, [C,4] i32
     tid, prev, attempt, best, info = torch.ops.frhip.live_tracks(bbox, det_blur, frame_offsets, clip_offsets,
                                                                  100.0, 30, 3, 10)              # [N] x 4, [C,4] i32
+    attempt, best, state, info = torch.ops.frhip.server_tracks(det_blur, clock, order, track_offsets,
+                                                               3, 10, 10.0, 0.6)                # [N] x 3, [T,4] i32
     scores = torch.ops.frhip.identity_scores(q, gallery_rows, id_offsets, "mean", 3)   # [N, n_ids] f32
     rec_i, rec_f, counts = torch.ops.frhip.eval_probes(scores, true_id, thresholds)    # [N,4] x 2, [T,4] i64
 
@@ -65,7 +67,7 @@ _utility: Dict[torch.device, "_lib.Handle"] = {}
 
 def utility_handle(device) -> "_lib.Handle":
     """A model-less handle on ``device`` for the entry points that need no weights
-    (``augment_faces``, ``track_consensus``, ``capture_tracks``, ``live_tracks``, ``identity_scores``, ``eval_probes``): one per device, created on first use."""
+    (``augment_faces``, ``track_consensus``, ``capture_tracks``, ``live_tracks``, ``server_tracks``, ``identity_scores``, ``eval_probes``): one per device, created on first use."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
@@ -199,6 +201,23 @@ def _(bbox, metrics, frame_offsets, clip_offsets, max_distance, recognition_inte
     return (bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((n,), dtype=torch.int32),
             bbox.new_empty((n,), dtype=torch.int32), bbox.new_empty((n,), dtype=torch.int32),
             bbox.new_empty((c, 4), dtype=torch.int32))
+
+
+@torch.library.custom_op("frhip::server_tracks", mutates_args=())
+def server_tracks(metrics: torch.Tensor, clock: torch.Tensor, order: torch.Tensor, track_offsets: List[int],
+                  max_attempts: int, buffer_size: int, retry_cooldown: float, det_gate: float
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    if metrics.device.type != "cuda":
+        raise ValueError(f"metrics are on {metrics.device}: server_tracks runs on a HIP device (no CPU fallback)")
+    return utility_handle(metrics.device).server_tracks(metrics, clock, order, track_offsets, max_attempts,
+                                                        buffer_size, retry_cooldown, det_gate)
+
+
+@server_tracks.register_fake
+def _(metrics, clock, order, track_offsets, max_attempts, buffer_size, retry_cooldown, det_gate):
+    n, t = metrics.shape[0], max(len(track_offsets) - 1, 0)
+    return (metrics.new_empty((n,), dtype=torch.int32), metrics.new_empty((n,), dtype=torch.int32),
+            metrics.new_empty((n,), dtype=torch.int32), metrics.new_empty((t, 4), dtype=torch.int32))
 
 
 @torch.library.custom_op("frhip::identity_scores", mutates_args=())

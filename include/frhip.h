@@ -287,6 +287,56 @@ int fr_live_tracks(fr_handle* h,
                    int32_t* best,     /* device [total] */
                    int32_t* clip_info /* device [n_clips][4] */, void* stream);
 
+/* Server sessions: the gating, the retry cooldown and the frame selection of the server's
+ * LiveRecognitionTracker (face_recognition_server.py:23-124) as process_faces / process_full_frame
+ * drive it (:368-413, :638-678), for every track of a recorded request log in one launch.  Track ids
+ * come from outside, so tracks do not interact: the log's n_dets detections are grouped by track,
+ * track t = order[track_offsets[t] .. track_offsets[t+1]), detection indices in arrival order.  Per
+ * appearance, with now = clock[d] (the request's clock, the same for all faces of a request):
+ *   FR_SERVER_COOLDOWN      the track is in cooldown and now < deadline.
+ *   FR_SERVER_RESET         in cooldown and now >= deadline: the cooldown ends, the cycle's attempts
+ *                           go to 0 and the ring is emptied, this appearance included (no attempt).
+ *   FR_SERVER_COOLDOWN_SET  the cycle's attempts reached max_attempts: deadline = now +
+ *                           retry_cooldown (one double addition).  So a cooldown starts on the first
+ *                           appearance after the last failed attempt.
+ *   FR_SERVER_ATTEMPT       otherwise, when the best face of the window has det_score > det_gate.
+ *   FR_SERVER_GATED         otherwise.
+ * The window is the last min(appearances since the run start, buffer_size) appearances, this one
+ * included; a run starts at the track's first appearance and after every reset.  The best face is the
+ * one of largest key = (double)det_score * min(blur_score / 100.0, 1.0), without contraction, the
+ * oldest of equal keys.  attempt[d] = the 0-based ordinal of the attempt among all attempts of the
+ * track, through cooldown cycles, as if no earlier attempt had succeeded (the caller drops what
+ * follows a success); best[d] = the detection the attempt embeds; both -1 without an attempt.
+ * track_info[t] = {attempts, cooldowns set, resets, error}.  A track with a non-finite metric or
+ * clock (FR_SERVER_ERR_VALUE) or an order entry outside [0, n_dets) (FR_SERVER_ERR_ORDER) gets
+ * {0, 0, 0, error}, -1 / -1 / FR_SERVER_GATED on its detections, the other tracks their results, and
+ * the call returns FR_ERR_UNSUPPORTED after its synchronisation.  Detections no track names are not
+ * written.  Deterministic.  Any handle will do, finalised or not.  Synchronises (the offsets are
+ * staged from the host).  n_tracks == 0 is a no-op.  NULL buffers, n_tracks < 0, n_dets < 0, offsets
+ * that do not start at 0 or that decrease, max_attempts outside [1, FR_SERVER_MAX_ATTEMPTS],
+ * buffer_size outside [1, FR_SERVER_MAX_BUFFER], retry_cooldown negative or not finite and det_gate
+ * not finite -> FR_ERR_INVALID_ARGUMENT (checked before the handle, so also reported for h == NULL). */
+#define FR_SERVER_MAX_ATTEMPTS 16 /* max_attempts */
+#define FR_SERVER_MAX_BUFFER 64   /* buffer_size */
+#define FR_SERVER_GATED 0
+#define FR_SERVER_ATTEMPT 1
+#define FR_SERVER_COOLDOWN 2
+#define FR_SERVER_COOLDOWN_SET 3
+#define FR_SERVER_RESET 4
+#define FR_SERVER_ERR_VALUE 1
+#define FR_SERVER_ERR_ORDER 2
+int fr_server_tracks(fr_handle* h,
+                     const double* metrics,        /* device [n_dets][2] det_score, blur_score */
+                     const double* clock,          /* device [n_dets] seconds */
+                     const int32_t* order,         /* device [track_offsets[n_tracks]] */
+                     const int32_t* track_offsets, /* host [n_tracks + 1] */
+                     int n_tracks, int n_dets, int max_attempts, int buffer_size, double retry_cooldown,
+                     double det_gate,
+                     int32_t* attempt,   /* device [n_dets] */
+                     int32_t* best,      /* device [n_dets] */
+                     int32_t* state,     /* device [n_dets] */
+                     int32_t* track_info /* device [n_tracks][4] */, void* stream);
+
 /* Model evaluation, step 1 (evaluate_models_v2.ipynb: cosine_similarity, aggregate_max / _mean /
  * _topk as identify_probe applies them): the score of every probe against every identity of a
  * multi-embedding gallery.  Q: device [n][512]; E: device [G][512], an explicit matrix (the handle's
