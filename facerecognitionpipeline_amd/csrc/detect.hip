@@ -493,10 +493,10 @@ __global__ __launch_bounds__(256) void det_stem_mfma_kernel(const uint8_t* __res
 }
 
 hipError_t launch_det_stem(const uint8_t* img, int n, int H, int W, int C, const float* w27xC, const float* scale,
-                           const float* shift, float* y, hipStream_t s) {
+                           const float* shift, float* y, hipStream_t s, bool force_scalar) {
   if (n <= 0) return hipSuccess;
-  if (C % 8 != 0 || C > 32 || H % 2 || W % 2) return hipErrorInvalidValue;
-  if ((C == 16 || C == 32) && W % 32 == 0 && (H / 2) % 2 == 0) {
+  if (C < 8 || C % 8 != 0 || C > 32 || H < 2 || W < 2 || H % 2 || W % 2) return hipErrorInvalidValue;
+  if (!force_scalar && (C == 16 || C == 32) && W % 32 == 0 && (H / 2) % 2 == 0) {
     const size_t lds = (256 + 5 * (W + 2) * 3 + 1) * sizeof(float);
     if (C == 32)
       hipLaunchKernelGGL(det_stem_mfma_kernel<2>, dim3(n * (H / 4)), dim3(256), lds, s, img, H, W, w27xC, scale, shift,

@@ -341,7 +341,9 @@ int detector_finalize(fr_handle* h) {
   take((void**)&d->pool, B * hw[0] * pad32(STEM) * f4);  // the largest: stage 2's input pooled to 80x80
   take((void**)&d->tA, B * hw[0] * hc * f4);
   take((void**)&d->tB, B * hw[0] * hc * f4);
-  d->dets_cap = 1024;
+  // a frame keeps at most its DET_MAX_CANDIDATES candidates: every row fr_detect promises
+  // (i < min(counts[f], max_faces), frhip.h) exists on the device
+  d->dets_cap = DET_MAX_CANDIDATES;
   take((void**)&d->cand, B * DET_MAX_CANDIDATES * 16 * f4);
   take((void**)&d->count, B * sizeof(int));
   take((void**)&d->dets, B * d->dets_cap * 15 * f4);
@@ -667,13 +669,16 @@ namespace {
 
 // decode + NMS of the B head maps in d->hd, then the detections of frames [off, off + B) to the host.
 // Decode divides by scales[b] (device, per frame) or, when scales is NULL, by det_scale.  `what` names
-// a frame in the DET_MAX_CANDIDATES error.  Synchronises.
+// a frame in the DET_MAX_CANDIDATES error.  counts[] is the full kept count; rows i < min(counts[f],
+// max_faces) of dets are written, for any max_faces >= 0.  Synchronises.
 int postprocess_chunk(fr_handle* h, int B, int off, float det_scale, const float* scales, const char* what,
                       float det_thresh, int max_faces, float* dets, int32_t* counts, hipStream_t s) {
   Detector* d = h->det;
   const int DW = d->det_w, DH = d->det_h;
   const int lh[3] = {DH / 8, DH / 16, DH / 32}, lw[3] = {DW / 8, DW / 16, DW / 32};
-  const int fmax = std::min(max_faces, d->dets_cap);
+  // rows per frame that nms_kernel writes and the host copies: the caller's max_faces (the kernel
+  // counts the detections it has no row for), at least 1 so that the copy is never empty
+  const int fmax = std::max(1, std::min(max_faces, d->dets_cap));
   FR_HIP(h, hipMemsetAsync(d->count, 0, B * sizeof(int), s));
   DetDecodeParams dp{};
   int base = 0;
@@ -693,9 +698,9 @@ int postprocess_chunk(fr_handle* h, int B, int off, float det_scale, const float
   dp.cand = d->cand;
   hipError_t e = launch_decode(dp, B, s);
   if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("decode: ") + hipGetErrorString(e));
-  e = launch_nms(d->cand, d->count, B, DET_MAX_CANDIDATES, 0.4f, d->dets_cap, d->dets, d->dets_count, s);
+  e = launch_nms(d->cand, d->count, B, DET_MAX_CANDIDATES, 0.4f, fmax, d->dets, d->dets_count, s);
   if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("nms: ") + hipGetErrorString(e));
-  std::vector<float> hbuf((size_t)B * d->dets_cap * 15);
+  std::vector<float> hbuf((size_t)B * fmax * 15);
   std::vector<int> hcnt(B), hraw(B);
   FR_HIP(h, hipMemcpyAsync(hbuf.data(), d->dets, hbuf.size() * sizeof(float), hipMemcpyDeviceToHost, s));
   FR_HIP(h, hipMemcpyAsync(hcnt.data(), d->dets_count, B * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -707,9 +712,10 @@ int postprocess_chunk(fr_handle* h, int B, int off, float det_scale, const float
                   std::string(what) + " " + std::to_string(off + b) + " has " + std::to_string(hraw[b]) +
                       " anchors above det_thresh (limit " + std::to_string(DET_MAX_CANDIDATES) + ")");
     counts[off + b] = hcnt[b];
-    const int k = std::min(hcnt[b], fmax);
-    std::memcpy(dets + ((size_t)(off + b) * max_faces) * 15, hbuf.data() + (size_t)b * d->dets_cap * 15,
-                (size_t)k * 15 * sizeof(float));
+    const int k = std::min(hcnt[b], std::min(max_faces, fmax));
+    if (k > 0)
+      std::memcpy(dets + ((size_t)(off + b) * max_faces) * 15, hbuf.data() + (size_t)b * fmax * 15,
+                  (size_t)k * 15 * sizeof(float));
   }
   return FR_OK;
 }
@@ -762,6 +768,25 @@ int detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int
   rc = forward_chunk(h, frames, n, height, width, g, s);
   if (rc) return rc;
   return copy_heads_canvas(h, n, g, heads, canvas, s);
+}
+
+int detector_postprocess(fr_handle* h, const float* heads, int n, float det_scale, const float* det_scales,
+                         float det_thresh, int max_faces, float* dets, int32_t* counts, hipStream_t s) {
+  Detector* d = h->det;
+  if (n > d->max_frames) return fail(h, FR_ERR_INVALID_ARGUMENT, "n exceeds the handle's max_batch");
+  size_t off = 0;
+  for (int i = 0; i < 3; ++i) {
+    const size_t bytes = (size_t)n * (d->det_h >> (3 + i)) * (d->det_w >> (3 + i)) * 32 * sizeof(float);
+    FR_HIP(h, hipMemcpyAsync(d->hd[i], (const char*)heads + off, bytes, hipMemcpyDeviceToDevice, s));
+    off += bytes;
+  }
+  const float* scales = nullptr;
+  if (det_scales) {  // staged in the image-descriptor buffer, where detector_run_images keeps its scales
+    if (int rc = ensure_buf(h, &d->imgs, &d->imgs_cap, (size_t)n * sizeof(float))) return rc;
+    FR_HIP(h, hipMemcpyAsync(d->imgs, det_scales, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+    scales = static_cast<const float*>(d->imgs);
+  }
+  return postprocess_chunk(h, n, 0, det_scale, scales, "frame", det_thresh, max_faces, dets, counts, s);
 }
 
 int detector_check_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n) {

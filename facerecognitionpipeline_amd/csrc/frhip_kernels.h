@@ -390,8 +390,9 @@ struct CropImage {
 hipError_t launch_resize_images(const CropImage* imgs, const int* tabs, int n, int simd_end, uint8_t* out,
                                 hipStream_t s);
 // (x - 127.5)/128 -> conv3x3 s2 p1 3->C (C % 8 == 0, <= 32; weights [27][C]) -> BN -> ReLU, NHWC.
+// force_scalar: det_stem_kernel also where the MFMA kernel would run (tests compare the two).
 hipError_t launch_det_stem(const uint8_t* img, int n, int H, int W, int C, const float* w27xC, const float* scale,
-                           const float* shift, float* y, hipStream_t s);
+                           const float* shift, float* y, hipStream_t s, bool force_scalar = false);
 hipError_t launch_maxpool3(const float* x, int B, int H, int W, int C, float* y, hipStream_t s);
 hipError_t launch_upsample_add(float* big, const float* small, int B, int h, int w, int C, hipStream_t s);
 // AvgPool2d(2, 2), NHWC, even H and W, C % 4 == 0.

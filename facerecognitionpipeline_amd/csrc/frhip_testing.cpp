@@ -334,6 +334,58 @@ int frt_maxpool3(const float* x, int B, int H, int W, int C, float* y, void* str
   return FR_OK;
 }
 
+int frt_upsample_add(float* big, const float* small, int B, int h, int w, int C, void* stream) {
+  if (B < 1 || h < 1 || w < 1 || C < 4 || !big || !small)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_upsample_add: bad arguments");
+  const hipError_t e = launch_upsample_add(big, small, B, h, w, C, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_upsample_add: refused");
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_upsample_add: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_avgpool2(const float* x, int B, int H, int W, int C, float* y, void* stream) {
+  if (B < 1 || H < 2 || W < 2 || C < 4 || !x || !y ||
+      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_avgpool2: bad arguments");
+  const hipError_t e = launch_avgpool2(x, B, H, W, C, y, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_avgpool2: refused");
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_avgpool2: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_row_expand(const float* x, int B, int Hs, int W, int C, int m, int Hd, float* y, void* stream) {
+  if (B < 1 || W < 1 || C < 4 || !x || !y || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_row_expand: bad arguments");
+  const hipError_t e = launch_row_expand(x, B, Hs, W, C, m, Hd, y, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_row_expand: refused");
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_row_expand: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_det_stem(const uint8_t* img, int B, int H, int W, int C, const float* w27xC, const float* scale,
+                 const float* shift, float* y, int force_scalar, void* stream) {
+  if (B < 1 || !img || !w27xC || !scale || !shift || !y || (reinterpret_cast<uintptr_t>(y) & 15) ||
+      (reinterpret_cast<uintptr_t>(img) & 3))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_det_stem: bad arguments");
+  const hipError_t e =
+      launch_det_stem(img, B, H, W, C, w27xC, scale, shift, y, (hipStream_t)stream, force_scalar != 0);
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_det_stem: refused");
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_det_stem: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_detector_postprocess(fr_handle* h, const float* heads, int n, float det_scale, const float* det_scales,
+                             float det_thresh, int max_faces, float* dets, int32_t* counts, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->detector || !h->finalized) return fail(h, FR_ERR_STATE, "not a finalised detector handle");
+  if (n < 1 || !heads || !counts || max_faces < 0 || (max_faces > 0 && !dets))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad arguments");
+  DeviceGuard dg(h->device);
+  return detector_postprocess(h, heads, n, det_scale, det_scales, det_thresh, max_faces, dets, counts,
+                              (hipStream_t)stream);
+}
+
 int frt_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, void* stream) {
   if (k < 1 || k > G) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_topk: k must be in [1, G]");
   hipError_t e = launch_topk(scores, n, G, k, idx, val, (hipStream_t)stream);

@@ -479,5 +479,10 @@ int detector_run_images(fr_handle* h, const uint8_t* const* images, const int32_
                         int max_faces, float* dets, int32_t* counts, hipStream_t s);
 int detector_forward_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* heads,
                             uint8_t* canvas, hipStream_t s);
+// The post-processing alone (frhip_testing.h: frt_detector_postprocess): heads (device, n <= max_frames
+// frames in detector_forward's layout) into the detector's head buffers, then postprocess_chunk with
+// det_scale or, when det_scales (host [n]) is given, with those uploaded as the per-frame scales.
+int detector_postprocess(fr_handle* h, const float* heads, int n, float det_scale, const float* det_scales,
+                         float det_thresh, int max_faces, float* dets, int32_t* counts, hipStream_t s);
 
 }  // namespace frhip_rt

@@ -422,7 +422,9 @@ int fr_blur_scores(fr_handle* h, const uint8_t* crops, int n, int height, int wi
  * frames: device uint8 [n][height][width][3] RGB.  Per frame f, counts[f] = detections
  * after NMS (score order) and dets[f][i][0..14] = x1 y1 x2 y2 score, then 5 landmarks
  * (x, y), in frame pixels, for i < min(counts[f], max_faces) (host buffers; synchronises).
- * More than 4096 anchors above det_thresh in one frame -> FR_ERR_UNSUPPORTED. */
+ * That holds for every max_faces >= 0 (a frame keeps at most 4096 detections, and the
+ * detector's own buffer holds that many); rows from min(counts[f], max_faces) on are not
+ * written.  More than 4096 anchors above det_thresh in one frame -> FR_ERR_UNSUPPORTED. */
 int fr_detect(fr_handle* h, const uint8_t* frames, int n, int height, int width, float det_thresh, int max_faces,
               float* dets, int32_t* counts, void* stream);
 

@@ -118,6 +118,20 @@ int frt_fit_similarity(const float* src, const float* dst, int n, double* M);
 /* The detector stem's MaxPool2d(3, 2, 1) alone: x [B][H][W][C] -> y [B][(H+1)/2][(W+1)/2][C], NHWC
  * f32, C % 4 == 0, 16-byte aligned.  Asynchronous on stream. */
 int frt_maxpool3(const float* x, int B, int H, int W, int C, float* y, void* stream);
+/* The detector's other glue kernels alone (detect.hip), NHWC f32, C % 4 == 0, 16-byte aligned,
+ * asynchronous on stream; arguments the launchers refuse -> FR_ERR_INVALID_ARGUMENT.
+ * frt_upsample_add: big [B][2h][2w][C] += nearest-2x(small [B][h][w][C]) (the FPN top-down add).
+ * frt_avgpool2:     y [B][H/2][W/2][C] = AvgPool2d(2, 2)(x [B][H][W][C]); even H and W.
+ * frt_row_expand:   y [B][Hd][W][C]: row r of x [B][Hs][W][C] above row m, Hd - Hs + 1 copies of row
+ *                   m, then the rows below it (detector.cpp row_plan); 0 <= m < Hs <= Hd. */
+int frt_upsample_add(float* big, const float* small, int B, int h, int w, int C, void* stream);
+int frt_avgpool2(const float* x, int B, int H, int W, int C, float* y, void* stream);
+int frt_row_expand(const float* x, int B, int Hs, int W, int C, int m, int Hd, float* y, void* stream);
+/* The detector stem alone: y [B][H/2][W/2][C] = relu(conv3x3 s2 p1((img - 127.5) / 128) * scale + shift),
+ * img uint8 [B][H][W][3], w27xC the repacked [ky][kx][c][C] weight; C in {8, 16, 24, 32}, even H, W.
+ * C = 16 / 32 with W % 32 == 0 and even H / 2 run the MFMA kernel unless force_scalar. */
+int frt_det_stem(const uint8_t* img, int B, int H, int W, int C, const float* w27xC, const float* scale,
+                 const float* shift, float* y, int force_scalar, void* stream);
 
 /* Row-wise top-k of a [n][G] score matrix (score desc, equal scores by descending index; k in [1, G]). */
 int frt_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, void* stream);
@@ -140,6 +154,14 @@ int frt_detector_forward(fr_handle* h, const uint8_t* frames, int n, int height,
  * canvas as above, canvas i the full 640-row canvas of image i.  Synchronises. */
 int frt_detector_forward_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* heads,
                                 uint8_t* canvas, void* stream);
+/* The post-processing of fr_detect / fr_detect_images alone, on caller-supplied head maps: heads
+ * (device, the layout frt_detector_forward writes, n <= max_frames frames) is copied into the
+ * detector's own head buffers and the product's decode + sort + NMS + copy-out runs on them.
+ * det_scales: NULL (every frame decodes with det_scale, as fr_detect does) or a host array of n
+ * per-frame scales (uploaded and handed to the kernel, as fr_detect_images does).  dets: host
+ * [n][max_faces][15], counts: host [n], as fr_detect fills them.  Synchronises. */
+int frt_detector_postprocess(fr_handle* h, const float* heads, int n, float det_scale, const float* det_scales,
+                             float det_thresh, int max_faces, float* dets, int32_t* counts, void* stream);
 /* A/B: the stem and stage 1 skip the letterbox's invariant bottom rows (on, the default) or run
  * the full 640-row canvas (0).  Both compute the same network to fp32 rounding. */
 int frt_set_detector_row_reduction(fr_handle* h, int on);

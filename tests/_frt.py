@@ -58,6 +58,16 @@ def lib():
         L.frt_detector_forward.argtypes = [_P, _P, _I, _I, _I, _P, _P, _P]
         L.frt_set_detector_row_reduction.restype = _I
         L.frt_set_detector_row_reduction.argtypes = [_P, _I]
+        L.frt_upsample_add.restype = _I
+        L.frt_upsample_add.argtypes = [_P, _P, _I, _I, _I, _I, _P]
+        L.frt_avgpool2.restype = _I
+        L.frt_avgpool2.argtypes = [_P, _I, _I, _I, _I, _P, _P]
+        L.frt_row_expand.restype = _I
+        L.frt_row_expand.argtypes = [_P, _I, _I, _I, _I, _I, _I, _P, _P]
+        L.frt_det_stem.restype = _I
+        L.frt_det_stem.argtypes = [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]
+        L.frt_detector_postprocess.restype = _I
+        L.frt_detector_postprocess.argtypes = [_P, _P, _I, ctypes.c_float, _P, ctypes.c_float, _I, _P, _P, _P]
         L._frt_ready = True
     return L
 
@@ -108,6 +118,63 @@ def maxpool3(x):
     y = torch.full((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), float("nan"), device=x.device)
     _lib.check(lib().frt_maxpool3(_p(x), B, H, W, C, _p(y), torch.cuda.current_stream().cuda_stream))
     return y
+
+
+def upsample_add(big, small):
+    """big [B][2h][2w][C] + nearest-2x(small [B][h][w][C]) on the detector's kernel (big is not changed)."""
+    B, h, w, C = small.shape
+    out = big.clone()
+    _lib.check(lib().frt_upsample_add(_p(out), _p(small), B, h, w, C, torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def avgpool2(x):
+    """AvgPool2d(2, 2) of x [B][H][W][C] (NHWC cuda f32) on the detector's kernel."""
+    B, H, W, C = x.shape
+    y = torch.full((B, H // 2, W // 2, C), float("nan"), device=x.device)
+    _lib.check(lib().frt_avgpool2(_p(x), B, H, W, C, _p(y), torch.cuda.current_stream().cuda_stream))
+    return y
+
+
+def row_expand(x, m, Hd):
+    """x [B][Hs][W][C] -> [B][Hd][W][C] with row m repeated Hd - Hs more times (row_expand_kernel)."""
+    B, Hs, W, C = x.shape
+    y = torch.full((B, max(Hd, 0), W, C), float("nan"), device=x.device)
+    _lib.check(lib().frt_row_expand(_p(x), B, Hs, W, C, m, Hd, _p(y), torch.cuda.current_stream().cuda_stream))
+    return y
+
+
+def det_stem(img, w27xC, scale, shift, force_scalar=False):
+    """The detector stem on img uint8 [B][H][W][3] (cuda), w27xC f32 [27][C]: y [B][H/2][W/2][C]."""
+    B, H, W, _ = img.shape
+    C = w27xC.shape[1]
+    y = torch.full((B, H // 2, W // 2, C), float("nan"), device=img.device)
+    _lib.check(lib().frt_det_stem(_p(img), B, H, W, C, _p(w27xC), _p(scale), _p(shift), _p(y), int(force_scalar),
+                                  torch.cuda.current_stream().cuda_stream))
+    return y
+
+
+def detector_postprocess(handle, heads, det_scale=1.0, det_scales=None, det_thresh=0.5, max_faces=256):
+    """The product's decode + sort + NMS + copy-out on caller-supplied head maps.
+
+    heads: the three levels' maps, numpy f32 [n][hw][32] each.  det_scales: None or n per-frame scales.
+    Returns (dets f32 [n][max_faces][15] pre-filled with NaN, so rows the call did not write stay
+    visible, counts int32 [n] pre-filled with -1)."""
+    import numpy as np
+    n = heads[0].shape[0]
+    flat = np.concatenate([np.ascontiguousarray(h, dtype=np.float32).reshape(-1) for h in heads])
+    dev = torch.from_numpy(flat).to(handle.device)
+    dets = np.full((n, max_faces, 15), np.nan, dtype=np.float32)
+    counts = np.full(n, -1, dtype=np.int32)
+    sc = None
+    if det_scales is not None:
+        sc = np.ascontiguousarray(det_scales, dtype=np.float32)
+        assert sc.shape == (n,)
+    rc = lib().frt_detector_postprocess(handle.h, _p(dev), n, float(det_scale), None if sc is None else sc.ctypes.data,
+                                        float(det_thresh), int(max_faces), dets.ctypes.data, counts.ctypes.data,
+                                        torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, handle.h)
+    return dets, counts
 
 
 def topk(scores, k):

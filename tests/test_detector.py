@@ -5,11 +5,12 @@ oracle/scrfd.py).  What is pinned:
 * CPU: the restated network's key schema == the product schema; its size
   (4.23 M params, 13.34 GMAC at 640x640) == the published SCRFD-10G figures;
   the cv2.resize restatement's algebra (identity, exact integer-ratio sampling);
-  NMS / decode on hand-built cases.
+  NMS / decode on hand-built cases; the preconditions of the planted head-map cases
+  (tests/_det_cases.py) that test_gpu_det_postprocess.py runs on the GPU.
 * GPU: letterboxed canvas bit-exact vs the restatement; the three head maps vs
   the PyTorch-CPU restatement (fp32, 1e-4 relative); final detections vs the
-  numpy post-processing run on the GPU's own head maps (same boxes to 1e-4 px,
-  same order); the FaceDetector / FaceProcessor API on top.
+  numpy post-processing run on the GPU's own head maps (the same boxes and landmarks
+  bitwise, same order); the FaceDetector / FaceProcessor API on top.
 """
 import numpy as np
 import pytest
@@ -58,6 +59,23 @@ def test_nms_restatement_hand_cases():
     # IoU exactly at the threshold is kept (ovr <= 0.4)
     a = np.array([[0, 0, 9, 9, 0.9], [0, 0, 9, 3, 0.8]], np.float32)   # areas 100 and 40, inter 40 -> 0.4
     assert R.nms(a) == [0, 1]
+
+
+def test_planted_postprocessing_cases_hold_their_preconditions():
+    """Every planted head-map case of tests/_det_cases.py (run on the GPU by test_gpu_det_postprocess.py)
+    builds: planted scores at least 1e-5 apart and from the threshold, the candidate and survivor counts
+    the restatement computes equal to the ones each case is meant to have."""
+    from tests import _det_cases as C
+    assert len(np.unique(C.GRID_SCORES)) == 4096 and np.diff(C.GRID_SCORES).min() >= 9.9e-5
+    cases = C.all_cases()
+    assert {c.name for c in cases} | {"clustered300", "clustered300#1"} == set(C.EXPECTED_COUNTS)
+    for c in cases:
+        assert (c.candidates, c.survivors) == C.EXPECTED_COUNTS[c.name]
+        for f, rows in enumerate(c.expected):
+            if rows is not None:                                       # score order, as the device sorts
+                assert np.all(np.diff(rows[:, 4].astype(np.float64)) <= 0), (c.name, f)
+    assert max(c.candidates[0] for c in cases) == 4096 and C.over_limit().candidates[1] == 4097
+    assert C.many_survivors().survivors == [1100]
 
 
 # ----------------------------------------------------------------------------- GPU
@@ -116,9 +134,11 @@ def test_detections_match_postprocessing_of_gpu_heads(det):
         n = int(counts[i])
         assert n == len(want) and n > 5
         got = dets[i, :n]
-        assert np.abs(got[:, :4] - want[:, :4]).max() <= 1e-4
+        # bitwise: decode_kernel and nms_kernel run the restatement's f32 operations in its order
+        assert np.array_equal(got[:, :4].view(np.uint32), want[:, :4].view(np.uint32))
         assert np.abs(got[:, 4] - want[:, 4]).max() <= 1e-6
-        assert np.abs(got[:, 5:].reshape(-1, 5, 2) - wkps).max() <= 1e-4
+        assert np.array_equal(np.ascontiguousarray(got[:, 5:]).view(np.uint32),
+                              np.ascontiguousarray(wkps.reshape(-1, 10)).view(np.uint32))
         total += n
     assert total > 20
 

@@ -8,7 +8,20 @@ output row, maps smaller than a strip, negative inputs (the padding never wins).
 The F(4x4) item shapes inside the detector network: with 8 frames the wide items run stage 2 and
 the stride-8 head towers, the tall items the stem conv (more than one round of 64-cout items each),
 and the forward must equal the 64-cout-items forward bitwise.
+
+upsample_add_kernel, avgpool2_kernel, row_expand_kernel: element-wise f32 kernels whose operation
+order is part of their comment, so each must equal the same expression in torch / numpy bitwise, at
+one pixel, at odd sizes that are no multiple of a block, and at the detector's own shapes; the
+launchers must refuse what the kernels cannot index (odd sizes, channels that are no float4s, a
+row outside the map).
+
+det_stem_kernel and det_stem_mfma_kernel: against a float64 conv of the normalised image, inside a
+bound derived from the kernels' arithmetic, at each side of launch_det_stem's dispatch (channel
+count, W % 32, parity of H / 2), and the MFMA kernel against the scalar one on the same inputs.
+
+decode_kernel and nms_kernel have a file of their own: tests/test_gpu_det_postprocess.py.
 """
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -34,6 +47,149 @@ def test_maxpool3_matches_torch(B, H, W, C):
     torch.cuda.synchronize()
     assert got.shape == ref.shape
     assert torch.equal(got.cpu(), ref)
+
+
+def _randn(seed, *shape):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+
+
+@pytest.mark.parametrize("B,h,w,C", [
+    (1, 1, 1, 4),      # one float4 of `small`, four of `big`
+    (3, 5, 7, 8),      # odd sizes, 840 threads: the last block is partial
+    (2, 20, 20, 64),   # the stride-32 level added into the stride-16 one
+])
+def test_upsample_add_matches_torch(B, h, w, C):
+    big, small = _randn(1, B, 2 * h, 2 * w, C), _randn(2, B, h, w, C)
+    up = F.interpolate(small.permute(0, 3, 1, 2), scale_factor=2, mode="nearest").permute(0, 2, 3, 1)
+    ref = big + up
+    got = _frt.upsample_add(big.cuda(), small.cuda())
+    torch.cuda.synchronize()
+    assert torch.equal(got.cpu(), ref)
+
+
+def test_upsample_add_refuses_channels_that_are_no_float4():
+    with pytest.raises(ValueError):
+        _frt.upsample_add(torch.zeros(1, 2, 2, 6).cuda(), torch.zeros(1, 1, 1, 6).cuda())
+
+
+AVGPOOL_SHAPES = [
+    (1, 2, 2, 4),      # one window
+    (3, 6, 10, 8),     # 90 threads; H / 2 odd
+    (2, 40, 40, 64),   # stage 3's input of a 640 x 640 canvas
+]
+
+
+@pytest.mark.parametrize("B,H,W,C", AVGPOOL_SHAPES)
+def test_avgpool2_is_its_expression_bitwise(B, H, W, C):
+    x = _randn(3, B, H, W, C)
+    p, q, u, v = x[:, 0::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 0::2], x[:, 1::2, 1::2]
+    ref = (((p + q) + u) + v) * 0.25
+    got = _frt.avgpool2(x.cuda())
+    torch.cuda.synchronize()
+    assert torch.equal(got.cpu(), ref)
+
+
+@pytest.mark.parametrize("B,H,W,C", AVGPOOL_SHAPES)
+def test_avgpool2_within_one_ulp_of_the_mean(B, H, W, C):
+    """Against F.avg_pool2d in double, within 1 ulp (np.spacing of the kernel's output).
+
+    The inputs are chosen so that 1 ulp is what the kernel's summation order guarantees: they are
+    non-negative (as the ReLU outputs the detector pools), so the partial sums grow and every rounding
+    is at most half an ulp of the final sum; and a window's top row holds multiples of 2^-6 below 8,
+    so p + q is exact.  That leaves two roundings, (p + q) + u and + v: at most 1 ulp of the sum, and
+    the * 0.25 is exact.  (General f32 inputs: three roundings, up to 1.5 ulp, and no bound in ulps at
+    all once signs cancel -- the bitwise test above is the one that pins those.)"""
+    g = torch.Generator().manual_seed(4)
+    x = torch.rand(B, H, W, C, generator=g) * 8
+    x[:, 0::2] = torch.floor(x[:, 0::2] * 64) / 64
+    ref = F.avg_pool2d(x.double().permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1)
+    got = _frt.avgpool2(x.cuda()).cpu()
+    ulp = torch.from_numpy(np.spacing(got.numpy())).double()
+    assert bool(((got.double() - ref).abs() <= ulp).all())
+
+
+@pytest.mark.parametrize("shape", [(1, 3, 2, 4), (1, 2, 3, 4), (1, 2, 2, 6)])
+def test_avgpool2_refuses_odd_sizes_and_ragged_channels(shape):
+    with pytest.raises(ValueError):
+        _frt.avgpool2(torch.zeros(*shape).cuda())
+
+
+@pytest.mark.parametrize("B,Hs,W,C,m,Hd", [
+    (1, 5, 3, 4, 0, 9),     # m = 0: the copies come first
+    (2, 6, 5, 8, 3, 10),    # a middle row
+    (1, 7, 2, 4, 6, 12),    # m = Hs - 1: the copies come last
+    (2, 4, 3, 8, 2, 4),     # Hd == Hs: the identity
+    (1, 1, 4, 4, 0, 5),     # a one-row map
+    (3, 5, 7, 16, 2, 8),    # three images, 672 threads
+    (2, 56, 80, 64, 50, 72),  # stage 1's output of a 1080p batch grown to stage 2's height
+])
+def test_row_expand_matches_index_arithmetic(B, Hs, W, C, m, Hd):
+    x = _randn(5, B, Hs, W, C)
+    r = np.arange(Hd)
+    ins = Hd - Hs
+    src = np.where(r < m, r, np.where(r < m + ins, m, r - ins))
+    ref = x.numpy()[:, src]
+    got = _frt.row_expand(x.cuda(), m, Hd)
+    torch.cuda.synchronize()
+    assert np.array_equal(got.cpu().numpy().view(np.uint32), ref.view(np.uint32))
+
+
+@pytest.mark.parametrize("shape,m,Hd", [
+    ((1, 4, 3, 6), 1, 6),    # C % 4 != 0
+    ((1, 4, 3, 4), 4, 6),    # m == Hs
+    ((1, 4, 3, 4), -1, 6),   # m < 0
+    ((1, 4, 3, 4), 1, 3),    # Hd < Hs
+])
+def test_row_expand_refuses_bad_arguments(shape, m, Hd):
+    with pytest.raises(ValueError):
+        _frt.row_expand(torch.zeros(*shape).cuda(), m, Hd)
+
+
+def _stem_takes_mfma(H, W, C):
+    """launch_det_stem's dispatch."""
+    return C in (16, 32) and W % 32 == 0 and (H // 2) % 2 == 0
+
+
+@pytest.mark.parametrize("B,H,W,C", [
+    (2, 8, 64, 32),     # MFMA, two channel blocks
+    (2, 8, 64, 16),     # MFMA, one channel block
+    (2, 8, 64, 8),      # scalar: one channel group
+    (2, 8, 64, 24),     # scalar: three channel groups
+    (2, 8, 48, 32),     # scalar: W % 32 != 0
+    (3, 6, 64, 32),     # scalar: H / 2 odd
+    (3, 6, 48, 16),     # scalar: both
+    (1, 640, 640, 32),  # MFMA at the detector's canvas (28 -> 32 channels)
+])
+def test_det_stem_matches_float64_conv(B, H, W, C):
+    """relu(conv3x3 s2 p1((x - 127.5) / 128) * scale + shift) in float64 against the kernel launch_det_stem
+    picks for the shape.  (x - 127.5) / 128 is exact in f32, so per output the kernel's error is that of
+    27 chained fmaf (each at most 2^-24 of sum |v w|), one affine fmaf, and the reference's own rounding:
+    |got - ref| <= 28 * 2^-24 * sum |v w| * |scale| + 2^-23 * |ref|, for every output -- the top and
+    bottom rows and the first and last columns, whose windows reach into the zero padding, included.
+    A shape the MFMA kernel takes is also run on the scalar kernel; the two outputs are compared."""
+    g = torch.Generator().manual_seed(100 * H + W + C)
+    img = torch.randint(0, 256, (B, H, W, 3), generator=g, dtype=torch.uint8)
+    w = torch.randn(27, C, generator=g) * 0.2
+    scale = (torch.rand(C, generator=g) + 0.5) * torch.where(torch.arange(C) % 5 == 4, -1.0, 1.0)
+    shift = torch.randn(C, generator=g) * 0.1
+    x = ((img.double() - 127.5) / 128).permute(0, 3, 1, 2)
+    wt = w.double().reshape(3, 3, 3, C).permute(3, 2, 0, 1)                 # [ky][kx][ci][C] -> [C][ci][ky][kx]
+    pre = F.conv2d(x, wt, stride=2, padding=1)
+    mag = F.conv2d(x.abs(), wt.abs(), stride=2, padding=1)
+    sc, sh = scale.double().view(1, C, 1, 1), shift.double().view(1, C, 1, 1)
+    ref = torch.relu(pre * sc + sh).permute(0, 2, 3, 1)
+    bound = (28 * 2.0 ** -24 * mag * sc.abs()).permute(0, 2, 3, 1) + 2.0 ** -23 * ref.abs()
+    dev = [t.cuda() for t in (img, w, scale, shift)]
+    got = _frt.det_stem(*dev).cpu()
+    assert got.shape == ref.shape and bool(torch.isfinite(got).all())
+    excess = (got.double() - ref).abs() - bound
+    assert float(excess.max()) <= 0, (float(excess.max()), np.unravel_index(int(excess.argmax()), ref.shape))
+    for edge in (got[:, 0], got[:, -1], got[:, :, 0], got[:, :, -1]):
+        assert float(edge.max()) > 0                                        # the halo outputs are real values
+    if _stem_takes_mfma(H, W, C):
+        scalar = _frt.det_stem(*dev, force_scalar=True).cpu()
+        print("largest |mfma - scalar|:", float((got - scalar).abs().max()))
+        assert torch.equal(got, scalar)
 
 
 def test_detector_item_shapes_are_bitwise_the_64_cout_items():

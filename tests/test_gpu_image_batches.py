@@ -142,7 +142,7 @@ def _order_sensitive(cand, logits):
             sw = rows.copy()
             sw[[p, p + 1]] = sw[[p + 1, p]]
             other = np.delete(sw[R._nms_sorted(sw[:, :5])], 4, axis=1)
-            if other.shape != kept.shape or np.abs(other - kept).max() > 1e-4:
+            if not np.array_equal(other, kept):
                 return True
     return False
 
@@ -150,7 +150,7 @@ def _order_sensitive(cand, logits):
 def test_decode_uses_each_images_scale(images, chunk_runs, all_dets):
     """The pattern of test_detector.test_detections_match_postprocessing_of_gpu_heads for every image of
     the nine-image call, with the image's own letterbox scale: counts equal, scores within 1e-6, boxes
-    and landmarks within 1e-4, in the reference's order.
+    and landmarks bitwise equal, in the reference's order.
 
     The exception is an image in which the reference's own result turns on a tie: swapping two
     candidates of different logits within TIE_GAP in score changes what its NMS keeps (_order_sensitive,
@@ -158,7 +158,7 @@ def test_decode_uses_each_images_scale(images, chunk_runs, all_dets):
     a pair differently, and NMS then keeps the other member of the cluster.  Seen on the GPU for 37x53, which is upscaled twelve times into flat
     blocks whose anchors score equal to the last bit: position 32 of 55, four candidates within 1e-6, the
     nearest 2.65 px away.  Such an image is held to the same count, the same scores in order within
-    1e-6, and every detection equal within 1e-4 to a reference pre-NMS candidate of its score (within
+    1e-6, and every detection's boxes and landmarks equal to a reference pre-NMS candidate of its score (within
     1e-6), decoded with this image's scale, one to one.  Images of at least two scales must take the
     ordered comparison."""
     dets, counts = all_dets
@@ -186,8 +186,9 @@ def test_decode_uses_each_images_scale(images, chunk_runs, all_dets):
                                      for lv in range(3)])
             assert logits.shape[0] == cand.shape[0]
             if not _order_sensitive(cand, logits):
-                assert np.abs(got[:, :4] - want[:, :4]).max() <= 1e-4, SIZES[i]
-                assert np.abs(got[:, 5:].reshape(-1, 5, 2) - wkps).max() <= 1e-4, SIZES[i]
+                assert np.array_equal(got[:, :4].view(np.uint32), want[:, :4].view(np.uint32)), SIZES[i]
+                assert np.array_equal(np.ascontiguousarray(got[:, 5:]).view(np.uint32),
+                                      np.ascontiguousarray(wkps.reshape(-1, 10)).view(np.uint32)), SIZES[i]
                 ordered.append(SIZES[i])
                 continue
             tied.append(SIZES[i])
@@ -196,7 +197,7 @@ def test_decode_uses_each_images_scale(images, chunk_runs, all_dets):
                 near = np.where(~used & (np.abs(cand[:, 4] - g[4]) <= 1e-6))[0]
                 assert near.size, (SIZES[i], p)
                 err = np.abs(np.delete(cand[near], 4, axis=1) - np.delete(g, 4)).max(axis=1)
-                assert err.min() <= 1e-4, (SIZES[i], p, float(err.min()))
+                assert err.min() == 0, (SIZES[i], p, float(err.min()))
                 used[near[int(err.argmin())]] = True
     print("ordered comparison asserted for:", ordered, "tie in the reference, candidates matched for:", tied)
     assert len({R.letterbox_geometry(*s)[2] for s in ordered}) >= 2, (ordered, tied)
