@@ -52,6 +52,10 @@ _SIGNATURES = {
                               _P]),
     "fr_identity_scores": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "fr_eval_probes": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "fr_samples_set": (_I, [_P, _P, _P, _I, _I, _P]),
+    "fr_samples_size": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "fr_match_identities": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "fr_embed_match_identities": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "fr_match_topk": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "fr_match_topk_host": (_I, [_P, _P, _I, _I, _P, _P]),
     "fr_embed_match": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
@@ -151,6 +155,7 @@ class Handle:
         idx = device.index if device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
         self.gallery_tag = None  # (owner, version) of the rows in HBM; see GalleryManager._sync_device
+        self.samples_tag = None  # the same for the sample gallery; see GalleryManager._sync_samples
         check(self._lib.fr_create(architecture.encode(), model_type.encode(), idx, int(max_batch), ctypes.byref(h)))
         self.h = h
 
@@ -427,6 +432,65 @@ class Handle:
                                            self.AGGREGATIONS[aggregation], int(k), ptr(out), ptr(sim),
                                            stream_of(self.device)), self.h)
         return (out, sim) if return_sim else out
+
+    # -- sample gallery / identity matching ---------------------------------
+    def samples_set(self, E: torch.Tensor, offsets, tag=None) -> None:
+        """The sample gallery of ``match_identities``: ``E`` f32 [G,512] (on the handle's device, or a
+        host tensor), identity i owning rows [offsets[i], offsets[i+1]) (1..1024 rows each).  Replaces
+        the previous one; no identities (``offsets`` of one entry) clears it.  The template gallery
+        (``gallery_set`` / ``match``) is not touched."""
+        if E.dtype != torch.float32 or E.dim() != 2 or (E.shape[0] and E.shape[1] != 512):
+            raise ValueError("expected E as a float32 [rows,512] tensor")
+        if E.device.type != "cpu":
+            self._require_device("E", E)
+        off, n_ids = _csr_offsets(offsets, E.shape[0], f"offsets must end at the {E.shape[0]} rows of E")
+        E = E.contiguous()
+        check(self._lib.fr_samples_set(self.h, ptr(E) if n_ids > 0 else None, off.ctypes.data, max(n_ids, 0),
+                                       int(E.device.type != "cpu"), stream_of(self.device)), self.h)
+        self.samples_tag = tag
+
+    def samples_size(self):
+        """(identities, rows) of the sample gallery; (0, 0) without one."""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        check(self._lib.fr_samples_size(self.h, ctypes.byref(a), ctypes.byref(b)), self.h)
+        return a.value, b.value
+
+    def _identity_args(self, aggregation: str, agg_k: int, k: int, n: int, idx: torch.Tensor, score: torch.Tensor,
+                       emb_out: Optional[torch.Tensor] = None) -> int:
+        if aggregation not in self.AGGREGATIONS:
+            raise ValueError(f"aggregation must be one of {sorted(self.AGGREGATIONS)}")
+        k = int(k)
+        if (idx.dtype != torch.int32 or score.dtype != torch.float32 or tuple(idx.shape) != (n, k)
+                or tuple(score.shape) != (n, k) or not idx.is_contiguous() or not score.is_contiguous()):
+            raise ValueError(f"idx / score must be contiguous int32 / float32 {[n, k]} tensors")
+        self._require_device("idx / score", idx, score)
+        if emb_out is not None:
+            if emb_out.dtype != torch.float32 or tuple(emb_out.shape) != (n, 512) or not emb_out.is_contiguous():
+                raise ValueError(f"emb_out must be a contiguous float32 {[n, 512]} tensor")
+            self._require_device("emb_out", emb_out)
+        return self.AGGREGATIONS[aggregation]
+
+    def match_identities(self, Q: torch.Tensor, aggregation: str, agg_k: int, k: int, idx: torch.Tensor,
+                         score: torch.Tensor) -> None:
+        """The ``k`` best identities of every query of ``Q`` f32 [n,512] against the sample gallery ->
+        ``idx`` int32 [n,k] (identity indices) / ``score`` f32 [n,k], descending, equal scores with the
+        lower index first; the scores are ``identity_scores``' (``aggregation`` "max" / "mean" / "topk",
+        ``agg_k`` <= 16 the top-k mean's k).  Asynchronous on the current stream."""
+        if Q.dtype != torch.float32 or Q.dim() != 2 or Q.shape[1] != 512 or not Q.is_contiguous():
+            raise ValueError("expected Q as a contiguous float32 [n,512] tensor")
+        self._require_device("Q", Q)
+        agg = self._identity_args(aggregation, agg_k, k, Q.shape[0], idx, score)
+        check(self._lib.fr_match_identities(self.h, ptr(Q), Q.shape[0], agg, int(agg_k), int(k), ptr(idx), ptr(score),
+                                            stream_of(self.device)), self.h)
+
+    def embed_match_identities(self, rgb: torch.Tensor, aggregation: str, agg_k: int, k: int, idx: torch.Tensor,
+                               score: torch.Tensor, emb_out: Optional[torch.Tensor] = None) -> None:
+        """``embed_match`` with ``match_identities`` in place of the template match, in one library
+        call: uint8 [n,112,112,3] crops -> idx / score [n,k] (and the normalised embeddings in
+        ``emb_out`` f32 [n,512])."""
+        agg = self._identity_args(aggregation, agg_k, k, rgb.shape[0], idx, score, emb_out)
+        check(self._lib.fr_embed_match_identities(self.h, ptr(rgb), rgb.shape[0], agg, int(agg_k), int(k), ptr(idx),
+                                                  ptr(score), ptr(emb_out), stream_of(self.device)), self.h)
 
     def eval_probes(self, scores: torch.Tensor, true_id: torch.Tensor, thresholds):
         """Per-probe records and threshold counts of a device score matrix ``scores`` f32 [n, n_ids]

@@ -27,6 +27,89 @@ long long capture_q_limit(double max_distance) {
 }
 
 int g_eval_chunk = 0;
+int g_identify_path = 0;
+int g_identify_tile_rows = IDENT_TILE_ROWS;
+
+// Tiles of the aggregation kernels: runs of whole identities of <= max_ids identities and <= max_rows
+// rows, an identity longer than max_rows alone; n_tiles + 1 boundaries (first identities, then n_ids).
+static std::vector<int32_t> cut_tiles(const int32_t* id_offsets, int n_ids, int max_ids, int max_rows) {
+  std::vector<int32_t> tiles;
+  for (int i = 0, first = 0; i <= n_ids; ++i) {
+    if (i == n_ids || (i > first && (i - first == max_ids || id_offsets[i + 1] - id_offsets[first] > max_rows))) {
+      tiles.push_back(first);
+      first = i;
+    }
+  }
+  tiles.push_back(n_ids);
+  return tiles;
+}
+
+// Probes per chunk of a score GEMM against G rows: score matrices below 2 GiB (the conv epilogue's
+// 32-bit offsets), or frt_set_eval_chunk's fewer.
+static int score_chunk(int n, int G) {
+  int nc = (int)std::max<long long>(1, std::min<long long>(n, ((1ll << 31) - 1) / ((long long)G * 4)));
+  if (g_eval_chunk > 0) nc = std::min(nc, g_eval_chunk);
+  return nc;
+}
+
+int match_identities_device(fr_handle* h, const float* Q, int n, int aggregation, int agg_k, int k, int32_t* idx,
+                            float* score, hipStream_t s) {
+  if (aggregation < FR_AGG_MAX || aggregation > FR_AGG_TOPK)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "aggregation must be FR_AGG_MAX, _MEAN or _TOPK");
+  if (aggregation == FR_AGG_TOPK && agg_k < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "agg_k must be >= 1");
+  if (aggregation == FR_AGG_TOPK && agg_k > EVAL_MAX_K)
+    return fail(h, FR_ERR_UNSUPPORTED, "top-k aggregation takes agg_k <= " + std::to_string(EVAL_MAX_K));
+  const int n_ids = h->sample_ids, G = h->sample_rows;
+  if (n_ids <= 0) return fail(h, FR_ERR_STATE, "sample gallery is empty (fr_samples_set first)");
+  if (k < 1 || k > n_ids) return fail(h, FR_ERR_INVALID_ARGUMENT, "k must be in [1, n_ids]");
+  if (n <= 0) return FR_OK;
+  // the fused kernel reads the gallery once per query: one query, or a few against a small gallery
+  const bool small = n == 1 || (n <= IDENT_SMALL_N && (long long)n * G <= IDENT_QUERY_ROWS);
+  const bool fused = g_identify_path == 0 ? small : g_identify_path == 1;
+  const int nc = fused ? n : score_chunk(n, G);
+  // [query norms: n][identity scores: nc x n_ids]
+  const size_t norm_floats = ((size_t)n + 3) & ~(size_t)3;
+  int rc = ensure_buf(h, &h->ident_ws, &h->ident_ws_cap, (norm_floats + (size_t)nc * n_ids) * sizeof(float));
+  if (rc) return rc;
+  float* d_qnorm = (float*)h->ident_ws;
+  float* d_out = d_qnorm + norm_floats;
+  if (fused) {
+    ProfScope ps(h, s, 0.0, 0);
+    hipError_t e = launch_match_small(Q, n, h->samples, h->d_sample_norm, h->d_sample_flag, h->d_sample_off, n_ids,
+                                      h->d_sample_tiles, h->sample_tiles, aggregation, agg_k, d_out, s);
+    if (e == hipSuccess) e = launch_topk(d_out, n, n_ids, k, idx, score, s, true);
+    if (e != hipSuccess) return launch_fail(h, "identity match", e);
+    return FR_OK;
+  }
+  // composed: the score GEMM into the scores workspace, fr_identity_scores' aggregation on the
+  // stored offsets, tiles and norms, then the top-k, a chunk of queries at a time
+  LaneWs& L = h->lane_ws[0];
+  if (ensure_stream_k(h->device, &h->cus, &L.sk_ws, &L.sk_ws_floats, &L.sk_cnt, &L.sk_cnt_cap) != FR_OK)
+    return fail(h, FR_ERR_HIP, "stream-K workspace allocation failed");
+  rc = ensure_buf(h, (void**)&h->scores, &h->scores_cap, (size_t)nc * G * sizeof(float));
+  if (rc) return rc;
+  {
+    ProfScope ps(h, s, 0.0, 0);
+    const hipError_t e = launch_row_norms(Q, n, d_qnorm, nullptr, s);
+    if (e != hipSuccess) return launch_fail(h, "row norms", e);
+  }
+  ConvW g;
+  g.w = h->samples;
+  g.geometry(512, G, 1, 1, 1, 0);
+  for (int q0 = 0; q0 < n; q0 += nc) {
+    const int qn = std::min(nc, n - q0);
+    // raw dots: no renormalisation of either side (the notebook's np.dot)
+    rc = run_conv(h, g, ConvCall{Q + (size_t)q0 * 512, h->scores, qn, 1, 1, EPI_RAW}, L, s);
+    if (rc) return rc;
+    ProfScope ps(h, s, 0.0, 0);
+    hipError_t e = launch_identity_agg(h->scores, qn, G, h->d_sample_off, n_ids, h->d_sample_eval_tiles,
+                                       h->sample_eval_tiles, d_qnorm + q0, h->d_sample_norm, h->d_sample_flag,
+                                       aggregation, agg_k, false, d_out, s);
+    if (e == hipSuccess) e = launch_topk(d_out, qn, n_ids, k, idx + (size_t)q0 * k, score + (size_t)q0 * k, s, true);
+    if (e != hipSuccess) return launch_fail(h, "identity match", e);
+  }
+  return FR_OK;
+}
 
 }  // namespace frhip_rt
 
@@ -242,15 +325,8 @@ int fr_identity_scores(fr_handle* h, const float* Q, int n, const float* E, cons
   hipStream_t s = (hipStream_t)stream;
   // tiles of the aggregation kernel: runs of identities of <= EVAL_TILE_IDS identities and
   // <= EVAL_TILE_ROWS rows (n_tiles + 1 boundaries), staged behind the offsets
-  std::vector<int32_t> tiles;
-  for (int i = 0, first = 0; i <= n_ids; ++i) {
-    if (i == n_ids || i - first == EVAL_TILE_IDS || id_offsets[i + 1] - id_offsets[first] > EVAL_TILE_ROWS) {
-      tiles.push_back(first);
-      first = i;
-    }
-  }
-  const int n_tiles = (int)tiles.size();
-  tiles.push_back(n_ids);
+  const std::vector<int32_t> tiles = cut_tiles(id_offsets, n_ids, EVAL_TILE_IDS, EVAL_TILE_ROWS);
+  const int n_tiles = (int)tiles.size() - 1;
   const int* d_stage[2];  // offsets, then tiles
   int rc = stage_int32(h, s, {{id_offsets, (size_t)n_ids + 1}, {tiles.data(), tiles.size()}}, d_stage);
   if (rc) return rc;
@@ -275,8 +351,7 @@ int fr_identity_scores(fr_handle* h, const float* Q, int n, const float* E, cons
   g.w = const_cast<float*>(E);
   g.geometry(512, G, 1, 1, 1, 0);
   // score matrices below 2 GiB (the conv epilogue's 32-bit offsets): probes in chunks
-  int nc = (int)std::max<long long>(1, std::min<long long>(n, ((1ll << 31) - 1) / ((long long)G * 4)));
-  if (g_eval_chunk > 0) nc = std::min(nc, g_eval_chunk);
+  const int nc = score_chunk(n, G);
   if (!sim) {
     rc = ensure_buf(h, (void**)&h->scores, &h->scores_cap, (size_t)nc * G * sizeof(float));
     if (rc) return rc;
@@ -321,6 +396,94 @@ int fr_eval_probes(fr_handle* h, const float* scores, int n, int n_ids, const in
   }
   FR_HIP(h, hipStreamSynchronize(s));  // the thresholds were staged from pageable host memory
   return FR_OK;
+}
+
+int fr_samples_set(fr_handle* h, const float* E, const int32_t* id_offsets, int n_ids, int src_is_device,
+                   void* stream) {
+  auto lk = lock_handle(h);
+  if (n_ids < 0 || (n_ids > 0 && (!E || !id_offsets)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n_ids or NULL buffer");
+  const std::string bad = csr_check(id_offsets, n_ids, 1, EVAL_MAX_ROWS, {"id_offsets", "identity", "gallery rows"});
+  if (!bad.empty()) return fail(h, FR_ERR_INVALID_ARGUMENT, bad);
+  const int G = n_ids > 0 ? id_offsets[n_ids] : 0;
+  if ((long long)G * 4 > (1ll << 31) - 1) return fail(h, FR_ERR_UNSUPPORTED, "one query's score row must stay below 2 GiB");
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  h->sample_ids = h->sample_rows = h->sample_tiles = h->sample_eval_tiles = 0;  // cleared until the new one is whole
+  if (n_ids == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const std::vector<int32_t> serve = cut_tiles(id_offsets, n_ids, INT32_MAX, g_identify_tile_rows);
+  const std::vector<int32_t> eval = cut_tiles(id_offsets, n_ids, EVAL_TILE_IDS, EVAL_TILE_ROWS);
+  // [flag][norms: G][offsets: n_ids + 1][serving tiles][evaluation tiles]
+  std::vector<int32_t> ints(id_offsets, id_offsets + n_ids + 1);
+  ints.insert(ints.end(), serve.begin(), serve.end());
+  ints.insert(ints.end(), eval.begin(), eval.end());
+  void* p = h->samples;
+  int rc = ensure_buf(h, &p, &h->samples_cap, (size_t)G * 512 * sizeof(float));
+  h->samples = (float*)p;
+  if (rc) return rc;
+  rc = ensure_buf(h, &h->sample_meta, &h->sample_meta_cap, (1 + (size_t)G + ints.size()) * sizeof(int32_t));
+  if (rc) return rc;
+  h->d_sample_flag = (int*)h->sample_meta;
+  h->d_sample_norm = (float*)h->sample_meta + 1;
+  h->d_sample_off = (int*)h->sample_meta + 1 + G;
+  h->d_sample_tiles = h->d_sample_off + n_ids + 1;
+  h->d_sample_eval_tiles = h->d_sample_tiles + serve.size();
+  FR_HIP(h, hipMemcpyAsync(h->samples, E, (size_t)G * 512 * sizeof(float),
+                           src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  FR_HIP(h, hipMemcpyAsync(h->d_sample_off, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  FR_HIP(h, hipMemsetAsync(h->d_sample_flag, 0, sizeof(int), s));
+  {
+    ProfScope ps(h, s, 0.0, 0);
+    const hipError_t e = launch_row_norms(h->samples, G, h->d_sample_norm, h->d_sample_flag, s);
+    if (e != hipSuccess) return launch_fail(h, "row norms", e);
+  }
+  FR_HIP(h, hipStreamSynchronize(s));  // the offsets and tiles were staged from pageable host memory
+  h->sample_ids = n_ids;
+  h->sample_rows = G;
+  h->sample_tiles = (int)serve.size() - 1;
+  h->sample_eval_tiles = (int)eval.size() - 1;
+  return FR_OK;
+}
+
+int fr_samples_size(fr_handle* h, int* n_ids, int* rows) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (n_ids) *n_ids = h->sample_ids;
+  if (rows) *rows = h->sample_rows;
+  return FR_OK;
+}
+
+int fr_match_identities(fr_handle* h, const float* Q, int n, int aggregation, int agg_k, int k, int32_t* idx,
+                        float* score, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (n < 0 || (n > 0 && (!Q || !idx || !score))) return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or NULL buffer");
+  if (int rc = check_dev_err(h)) return rc;  // reported by earlier asynchronous work
+  DeviceGuard dg(h->device);
+  return match_identities_device(h, Q, n, aggregation, agg_k, k, idx, score, (hipStream_t)stream);
+}
+
+int fr_embed_match_identities(fr_handle* h, const uint8_t* rgb, int n, int aggregation, int agg_k, int k,
+                              int32_t* idx, float* score, float* emb_out, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->detector) return fail(h, FR_ERR_STATE, "this handle is a detector (scrfd_10g); use fr_detect");
+  if (!h->finalized) return fail(h, FR_ERR_STATE, "model not finalised (fr_finalize)");
+  if (n < 0 || (n > 0 && (!rgb || !idx || !score))) return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or NULL buffer");
+  if (h->sample_ids <= 0) return fail(h, FR_ERR_STATE, "sample gallery is empty (fr_samples_set first)");
+  if (int rc = check_dev_err(h)) return rc;  // reported by earlier asynchronous work
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  float* emb = emb_out;
+  if (!emb) {
+    int rc = ensure_buf(h, &h->match_io, &h->match_io_cap, (size_t)n * 512 * sizeof(float));
+    if (rc) return rc;
+    emb = (float*)h->match_io;
+  }
+  int rc = embed_device(h, rgb, n, emb, 1, s);
+  if (rc) return rc;
+  return match_identities_device(h, emb, n, aggregation, agg_k, k, idx, score, s);
 }
 
 }  // extern "C"

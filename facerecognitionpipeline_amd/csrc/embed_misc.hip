@@ -278,30 +278,39 @@ hipError_t launch_l2norm_rows(const float* q, float* out, int n, int d, hipStrea
 // Equal scores rank the HIGHER gallery row first: that is np.argsort(s)[::-1] (the reference,
 // gallery_manager.py:197) whenever numpy's sort is stable -- its insertion sort for <= 16
 // elements, or kind="stable" -- i.e. a stable ascending sort, reversed.  (numpy's AVX-512
-// argsort leaves ties in no defined order)  NO_ROW ranks after any real row.
-constexpr int NO_ROW = -1;
-__device__ __forceinline__ bool ranks_before(float sa, int ia, float sb, int ib) {
-  return sa > sb || (sa == sb && ia > ib);
-}
+// argsort leaves ties in no defined order)  NONE ranks after any real row, FIRST
+// before every one.
+// LOW_FIRST (fr_match_identities): equal scores rank the LOWER index first, Python's stable
+// sorted(..., reverse=True) over the dict order in the notebook's identify_probe.
+template <bool LOW_FIRST>
+struct TieOrder {
+  static constexpr int NONE = LOW_FIRST ? 0x7fffffff : -1;
+  static constexpr int FIRST = LOW_FIRST ? -1 : 0x7fffffff;
+  static __device__ __forceinline__ bool before(float sa, int ia, float sb, int ib) {
+    return sa > sb || (sa == sb && (LOW_FIRST ? ia < ib : ia > ib));
+  }
+};
 
 // One wave per score row; k selection passes, each a strided scan for the best
 // element ranked strictly after the previous pick, then a wave arg-reduction.
 // Exact and order-independent (the result never depends on scan order).
+template <bool LOW_FIRST>
 __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ scores, int n, int G, int k,
                                                    int32_t* __restrict__ idx, float* __restrict__ val) {
+  using T = TieOrder<LOW_FIRST>;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
   const int lane = threadIdx.x & 63;
   const float* r = scores + (long long)row * G;
   float prev_s = INFINITY;
-  int prev_i = 0x7fffffff;  // ranks before every (score, row), +inf included
+  int prev_i = T::FIRST;  // ranks before every (score, row), +inf included
   for (int t = 0; t < k; ++t) {
     float bs = -INFINITY;
-    int bi = NO_ROW;
+    int bi = T::NONE;
     for (int g = lane; g < G; g += 64) {
       const float s = r[g];
       if (s != s) continue;  // NaN never ranks
-      if (ranks_before(prev_s, prev_i, s, g) && ranks_before(s, g, bs, bi)) {
+      if (T::before(prev_s, prev_i, s, g) && T::before(s, g, bs, bi)) {
         bs = s;
         bi = g;
       }
@@ -310,13 +319,13 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ sco
     for (int off = 32; off > 0; off >>= 1) {
       const float os = __shfl_xor(bs, off, 64);
       const int oi = __shfl_xor(bi, off, 64);
-      if (ranks_before(os, oi, bs, bi)) {
+      if (T::before(os, oi, bs, bi)) {
         bs = os;
         bi = oi;
       }
     }
     if (lane == 0) {
-      idx[(long long)row * k + t] = bi < 0 ? -1 : bi;
+      idx[(long long)row * k + t] = bi == T::NONE ? -1 : bi;
       val[(long long)row * k + t] = bs;
     }
     prev_s = bs;
@@ -327,22 +336,23 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ sco
 // Single-pass form for k <= KMAX: one 256-thread block per row.  Each thread keeps its
 // best KMAX (score, index) pairs of a strided slice in registers (unrolled insertion, no
 // runtime-indexed arrays), then k block-wide arg-max rounds pop the global best in order.
-template <int KMAX>
+template <int KMAX, bool LOW_FIRST>
 __device__ __forceinline__ void topk_row_small(const float* __restrict__ r, int G, int k, int32_t* __restrict__ idx,
                                                float* __restrict__ val, float* s_s, int* s_i) {
+  using T = TieOrder<LOW_FIRST>;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   float ls[KMAX];
   int li[KMAX];
 #pragma unroll
   for (int j = 0; j < KMAX; ++j) {
     ls[j] = -INFINITY;
-    li[j] = NO_ROW;
+    li[j] = T::NONE;
   }
   auto push = [&](float sv, int iv) {
-    if (sv != sv || !ranks_before(sv, iv, ls[KMAX - 1], li[KMAX - 1])) return;
+    if (sv != sv || !T::before(sv, iv, ls[KMAX - 1], li[KMAX - 1])) return;
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) {  // bubble the new pair into the sorted list
-      if (ranks_before(sv, iv, ls[j], li[j])) {
+      if (T::before(sv, iv, ls[j], li[j])) {
         const float ts = ls[j];
         const int ti = li[j];
         ls[j] = sv;
@@ -373,7 +383,7 @@ __device__ __forceinline__ void topk_row_small(const float* __restrict__ r, int 
     for (int off = 32; off > 0; off >>= 1) {
       const float os = __shfl_xor(bs, off, 64);
       const int oi = __shfl_xor(bi, off, 64);
-      if (ranks_before(os, oi, bs, bi)) {
+      if (T::before(os, oi, bs, bi)) {
         bs = os;
         bi = oi;
       }
@@ -387,34 +397,35 @@ __device__ __forceinline__ void topk_row_small(const float* __restrict__ r, int 
     bi = s_i[0];
 #pragma unroll
     for (int w = 1; w < 4; ++w)
-      if (ranks_before(s_s[w], s_i[w], bs, bi)) {
+      if (T::before(s_s[w], s_i[w], bs, bi)) {
         bs = s_s[w];
         bi = s_i[w];
       }
     __syncthreads();
     if (tid == 0) {
-      idx[t] = bi < 0 ? -1 : bi;
+      idx[t] = bi == T::NONE ? -1 : bi;
       val[t] = bs;
     }
-    if (li[0] == bi && bi >= 0) {  // indices are unique: exactly one owner pops
+    if (li[0] == bi && bi != T::NONE) {  // indices are unique: exactly one owner pops
 #pragma unroll
       for (int j = 0; j < KMAX - 1; ++j) {
         ls[j] = ls[j + 1];
         li[j] = li[j + 1];
       }
       ls[KMAX - 1] = -INFINITY;
-      li[KMAX - 1] = NO_ROW;
+      li[KMAX - 1] = T::NONE;
     }
   }
 }
 
-template <int KMAX>
+template <int KMAX, bool LOW_FIRST>
 __global__ __launch_bounds__(256) void topk_small_kernel(const float* __restrict__ scores, int G, int k,
                                                          int32_t* __restrict__ idx, float* __restrict__ val) {
   __shared__ float s_s[4];
   __shared__ int s_i[4];
   const int row = blockIdx.x;
-  topk_row_small<KMAX>(scores + (long long)row * G, G, k, idx + (long long)row * k, val + (long long)row * k, s_s, s_i);
+  topk_row_small<KMAX, LOW_FIRST>(scores + (long long)row * G, G, k, idx + (long long)row * k,
+                                  val + (long long)row * k, s_s, s_i);
 }
 
 // Serving-sized match scores: block (64 gallery rows, query q) of 256 threads.  The query is
@@ -471,14 +482,22 @@ hipError_t launch_scores_small(const float* q, const float* gallery, int G, floa
   return hipGetLastError();
 }
 
-hipError_t launch_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, hipStream_t s) {
+template <bool LOW_FIRST>
+static hipError_t launch_topk_order(const float* scores, int n, int G, int k, int32_t* idx, float* val,
+                                    hipStream_t s) {
   if (n <= 0 || k <= 0) return hipSuccess;
   if (k <= 8) {
-    hipLaunchKernelGGL(topk_small_kernel<8>, dim3(n), dim3(256), 0, s, scores, G, k, idx, val);
+    hipLaunchKernelGGL((topk_small_kernel<8, LOW_FIRST>), dim3(n), dim3(256), 0, s, scores, G, k, idx, val);
   } else {
-    hipLaunchKernelGGL(topk_kernel, dim3((n + 3) / 4), dim3(256), 0, s, scores, n, G, k, idx, val);
+    hipLaunchKernelGGL(topk_kernel<LOW_FIRST>, dim3((n + 3) / 4), dim3(256), 0, s, scores, n, G, k, idx, val);
   }
   return hipGetLastError();
+}
+
+hipError_t launch_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, hipStream_t s,
+                       bool low_index_first) {
+  return low_index_first ? launch_topk_order<true>(scores, n, G, k, idx, val, s)
+                         : launch_topk_order<false>(scores, n, G, k, idx, val, s);
 }
 
 }  // namespace frhip

@@ -13,7 +13,8 @@
 // at most EVAL_TILE_ROWS gallery rows.  The tile's slice of the probe's score row is contiguous; it
 // is loaded coalesced into LDS once, and each thread then owns identities of the tile and walks
 // their values in row order.  One-row identities therefore cost one thread each, not a wave, and a
-// 1024-row identity is one thread's loop.  Everything past the f32 loads is f32 compares or double
+// 1024-row identity is one thread's loop (identity_agg.h, shared with identify.hip's serving
+// kernel).  Everything past the f32 loads is f32 compares or double
 // sums in one fixed order that depends on nothing but the identity's row count, so out[p] depends
 // on nothing but sim[p] and the offsets.
 //
@@ -29,6 +30,8 @@
 
 #pragma clang fp contract(off)
 
+#include "identity_agg.h"
+
 namespace frhip {
 
 namespace {
@@ -36,8 +39,6 @@ namespace {
 constexpr int EVAL_BLOCK = 256;
 static_assert(EVAL_MAX_THRESHOLDS <= EVAL_BLOCK, "thread j owns threshold j");
 static_assert(EVAL_MAX_ROWS <= EVAL_TILE_ROWS, "an identity fits one tile");
-
-__device__ __forceinline__ bool unit_norm(float nrm) { return fabsf(nrm - 1.0f) < 0.01f; }
 
 // One wave per 512-float row.
 __global__ __launch_bounds__(EVAL_BLOCK) void row_norms_kernel(const float* __restrict__ x, int n,
@@ -90,37 +91,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void identity_agg_kernel(
   __syncthreads();
   for (int i = i0 + t; i < i1; i += EVAL_BLOCK) {
     const int a = offsets[i] - r0, b = offsets[i + 1] - r0;  // 1 <= b - a <= EVAL_MAX_ROWS
-    float res;
-    if (AGG == AGG_MAX) {
-      res = tile[a];
-      for (int r = a + 1; r < b; ++r) res = fmaxf(res, tile[r]);
-    } else if (AGG == AGG_MEAN) {
-      double s = 0.0;
-      for (int r = a; r < b; ++r) s += (double)tile[r];
-      res = (float)(s / (double)(b - a));
-    } else {
-      // the EVAL_MAX_K largest values in descending order (a value pushes the smaller ones down)
-      float top[EVAL_MAX_K];
-#pragma unroll
-      for (int j = 0; j < EVAL_MAX_K; ++j) top[j] = -INFINITY;
-      for (int r = a; r < b; ++r) {
-        float v = tile[r];
-        if (!(v > top[EVAL_MAX_K - 1])) continue;
-#pragma unroll
-        for (int j = 0; j < EVAL_MAX_K; ++j) {
-          const float hi = fmaxf(top[j], v);
-          v = fminf(top[j], v);
-          top[j] = hi;
-        }
-      }
-      const int m = min(k, b - a);
-      double s = 0.0;
-#pragma unroll
-      for (int j = 0; j < EVAL_MAX_K; ++j)
-        if (j < m) s += (double)top[j];
-      res = (float)(s / (double)m);
-    }
-    out[(long long)p * n_ids + i] = res;
+    out[(long long)p * n_ids + i] = aggregate_identity<AGG>(tile, a, b, k);
   }
 }
 

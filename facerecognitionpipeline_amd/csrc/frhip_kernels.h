@@ -213,8 +213,10 @@ hipError_t launch_l2norm_rows(const float* q, float* out, int n, int d, hipStrea
 // it, fused with the scores against the G x 512 gallery rows: scores [n][G]
 hipError_t launch_scores_small(const float* q, const float* gallery, int G, float* scores, int n, hipStream_t s);
 
-// Per row of a [n][G] score matrix: top-k by (score desc, index desc), k in [1, G].
-hipError_t launch_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, hipStream_t s);
+// Per row of a [n][G] score matrix: top-k by (score desc, index desc), k in [1, G]; with
+// low_index_first by (score desc, index asc), the order of fr_match_identities.
+hipError_t launch_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, hipStream_t s,
+                       bool low_index_first = false);
 
 // warpAffine INTER_LINEAR / BORDER_CONSTANT 0 of n crops from one uint8 RGB frame;
 // minv: device [n][6] inverse maps (double), out: [n][S][S][3].
@@ -352,6 +354,22 @@ hipError_t launch_identity_agg(float* sim, int n, int G, const int* offsets, int
 // device [n_thr] doubles; counts must be zero at launch.
 hipError_t launch_eval_probes(const float* scores, int n, int n_ids, const int* true_id, const double* thr, int n_thr,
                               int* rec_i, float* rec_f, long long* counts, hipStream_t s);
+
+// Identity matching (identify.hip: fr_match_identities' serving-sized path).  out[p][i] = the
+// aggregation of cosine_similarity(Q[p], E[r]) over identity i's rows r in [offsets[i], offsets[i+1]),
+// for n queries in one launch: what launch_identity_agg gives on the raw dots of Q and E, without
+// the [n][G] matrix.  enorm [G] / e_any_off as launch_row_norms wrote them for E; offsets: device
+// [n_ids + 1]; tiles: device [n_tiles + 1] first identities of runs of whole identities of
+// <= EVAL_MAX_ROWS rows (fr_samples_set cuts them at IDENT_TILE_ROWS rows, a longer identity alone).
+// Every query reads every row, so the launch costs n * G row reads.
+// fr_match_identities takes this kernel for one query, and for n <= IDENT_SMALL_N queries against G
+// rows with n * G <= IDENT_QUERY_ROWS; the composed path otherwise (all three measured)
+constexpr int IDENT_TILE_ROWS = 64;  // gallery rows of a serving tile
+constexpr int IDENT_SMALL_N = 16;
+constexpr long long IDENT_QUERY_ROWS = 65536;
+hipError_t launch_match_small(const float* Q, int n, const float* E, const float* enorm, const int* e_any_off,
+                              const int* offsets, int n_ids, const int* tiles, int n_tiles, int aggregation, int k,
+                              float* out, hipStream_t s);
 
 // ---- SCRFD detector glue (detect.hip)
 constexpr int DET_MAX_CANDIDATES = 4096;  // per frame, above det_thresh, before NMS

@@ -148,6 +148,16 @@ int frt_set_eval_chunk(int probes) {
   g_eval_chunk = probes;
   return FR_OK;
 }
+int frt_set_identify_path(int mode) {
+  if (mode < 0 || mode > 2) return FR_ERR_INVALID_ARGUMENT;
+  g_identify_path = mode;
+  return FR_OK;
+}
+int frt_set_identify_tile_rows(int rows) {
+  if (rows < 0 || rows > EVAL_MAX_ROWS) return FR_ERR_INVALID_ARGUMENT;
+  g_identify_tile_rows = rows == 0 ? IDENT_TILE_ROWS : rows;
+  return FR_OK;
+}
 int frt_set_s2_band(int on) {
   g_knobs.s2band = on != 0;
   return FR_OK;

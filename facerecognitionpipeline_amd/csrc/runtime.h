@@ -3,7 +3,8 @@
 //   frhip_runtime.cpp  the public fr_* C API (include/frhip.h): model, gallery rows, match, align,
 //                      detect, settings, profiling
 //   batch_ops.cpp      the fr_* calls over CSR batches: templates, track consensus, capture
-//                      and live sessions, identity scores, probe evaluation
+//                      and live sessions, identity scores, probe evaluation, the sample gallery
+//                      and identity matching
 //   finalize.cpp       handle and entry-point helpers, state-dict schema, BatchNorm folding, arenas,
 //                      workspace
 //   conv_dispatch.cpp  run_conv and its kernel-selection rules
@@ -198,6 +199,21 @@ struct fr_handle {
   // fr_eval_probes: the staged thresholds
   void* eval_ws = nullptr;
   size_t eval_ws_cap = 0;
+  // sample gallery (fr_samples_set): every enrolled row of every identity, beside the template
+  // gallery, and what a match needs of it, staged once: sample_meta = [off-unit flag][row norms:
+  // sample_rows][offsets: sample_ids + 1][serving tiles: sample_tiles + 1][evaluation tiles:
+  // sample_eval_tiles + 1] (d_sample_* point into it)
+  float* samples = nullptr;
+  size_t samples_cap = 0;
+  void* sample_meta = nullptr;
+  size_t sample_meta_cap = 0;
+  int sample_ids = 0, sample_rows = 0, sample_tiles = 0, sample_eval_tiles = 0;
+  int* d_sample_flag = nullptr;
+  float* d_sample_norm = nullptr;
+  int *d_sample_off = nullptr, *d_sample_tiles = nullptr, *d_sample_eval_tiles = nullptr;
+  // fr_match_identities: [query norms: n][identity scores: chunk x sample_ids]
+  void* ident_ws = nullptr;
+  size_t ident_ws_cap = 0;
 
   // alignment / quality workspace
   void* align_m = nullptr;  // [n][6] inverse affine maps (double), or fr_align_images' [n] WarpFace
@@ -312,6 +328,9 @@ struct fr_handle {
     (void)hipFree(gallery_tmp);
     (void)hipFree(csr_stage);
     (void)hipFree(eval_ws);
+    (void)hipFree(samples);
+    (void)hipFree(sample_meta);
+    (void)hipFree(ident_ws);
     (void)hipFree(align_m);
     (void)hipFree(blur_out);
     (void)hipFree(blur_ws);
@@ -410,8 +429,17 @@ int finalize_model(fr_handle* h);
 // in double (q = 4 x a squared centroid distance), so that q < q_limit is the reference's
 // `distance < max_distance`; 0 for max_distance <= 0 or NaN
 long long capture_q_limit(double max_distance);
-// frt_set_eval_chunk: probes per GEMM chunk of fr_identity_scores, 0 = the 2 GiB rule
+// frt_set_eval_chunk: probes per GEMM chunk of fr_identity_scores and of fr_match_identities'
+// composed path, 0 = the 2 GiB rule
 extern int g_eval_chunk;
+// frt_set_identify_path: 0 = fr_match_identities' rule (the fused kernel for small n x rows),
+// 1 = the fused kernel, 2 = the composed path, for every n
+extern int g_identify_path;
+// frt_set_identify_tile_rows: the row cap of the serving tiles the next fr_samples_set cuts
+extern int g_identify_tile_rows;
+// fr_match_identities under the handle's lock and device (fr_embed_match_identities' second half)
+int match_identities_device(fr_handle* h, const float* Q, int n, int aggregation, int agg_k, int k, int32_t* idx,
+                            float* score, hipStream_t s);
 
 // conv_dispatch.cpp
 // The geometry and K-step fields of conv cw over a B x H x W input in nsplit K-slices: what the

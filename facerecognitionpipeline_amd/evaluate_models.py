@@ -15,6 +15,10 @@ reference's recorded results), and ``aggregation='topk'`` with ``k > 16`` always
 statement for the scores.  ``pack_gallery`` packs and uploads a gallery dict once; every function
 accepts its result in place of the dict.
 
+``match_identities_host`` states ``fr_match_identities``' contract, the serving counterpart of the
+identity scores (the top-k identities of a query against a sample gallery resident in a handle), and
+``PackedGallery.to_samples(handle)`` makes an evaluated gallery that sample gallery.
+
 Two deviations from the notebook, both on purpose:
 
 * ``threshold_results`` is a list of row dicts in the reference's column order, not a DataFrame:
@@ -93,6 +97,22 @@ def identity_scores_host(sim: np.ndarray, offsets: Sequence[int], aggregation: s
             top = -np.sort(-seg, axis=1)[:, :m].astype(np.float64)
             out[:, i] = (np.cumsum(top, axis=1)[:, -1] / m).astype(np.float32)
     return out
+
+
+def match_identities_host(Q: np.ndarray, rows: np.ndarray, offsets: Sequence[int], aggregation: str = "mean",
+                          agg_k: int = 3, k: int = 3) -> Tuple[np.ndarray, np.ndarray]:
+    """What ``fr_match_identities`` returns for queries ``Q`` [n,512] against the sample gallery
+    (``rows`` [G,512], ``offsets``): ``(idx int32 [n,k], score float32 [n,k])``, the ``k`` largest of
+    ``identity_scores_host(similarity_matrix_host(Q, rows), offsets, aggregation, agg_k)`` per query in
+    descending order, equal scores with the lower identity index first (Python's stable
+    ``sorted(..., reverse=True)`` over the dict order in ``identify_probe``).  Any ``agg_k >= 1``."""
+    scores = identity_scores_host(similarity_matrix_host(Q, rows), offsets, aggregation, agg_k)
+    n, n_ids = scores.shape
+    k = int(k)
+    if k < 1 or k > n_ids:
+        raise ValueError(f"k must be in [1, {n_ids}]")
+    order = np.argsort(-scores, axis=1, kind="stable")[:, :k]  # stable: equal scores keep the index order
+    return order.astype(np.int32), np.take_along_axis(scores, order, axis=1)
 
 
 def eval_probes_host(scores: np.ndarray, true_id: Sequence[int], thresholds: Sequence[float]
@@ -274,6 +294,11 @@ class PackedGallery:
         if device not in self._dev:
             self._dev[device] = torch.from_numpy(self.rows).to(device)
         return self._dev[device]
+
+    def to_samples(self, handle, tag=None) -> None:
+        """Make this gallery the sample gallery of ``handle`` (``Handle.samples_set``): what an
+        evaluation scored is then what ``match_identities`` serves, identity i being ``names[i]``."""
+        handle.samples_set(self.rows_on(handle.device), self.offsets, tag)
 
 
 def pack_gallery(gallery_embeddings, device=None) -> PackedGallery:

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from .face_embedder import FaceEmbedder
-from .gallery_manager import GalleryManager, _slice_len
+from .gallery_manager import GalleryManager, _slice_len, check_identity_aggregation
 
 # include/frhip.h FR_TRACK_*
 TRACK_RECOGNIZED, TRACK_FEW_FRAMES, TRACK_NO_CONSENSUS, TRACK_BELOW_THRESHOLD = 0, 1, 2, 3
@@ -70,7 +70,15 @@ class FaceMatcher:
                  aggregation_method: str = "majority_vote", model_type: str = "adaface",
                  architecture: str = "ir_101", model_path: Optional[str] = None, device=None,
                  embedder: Optional[FaceEmbedder] = None, gallery: Optional[GalleryManager] = None,
-                 verbose: bool = True):
+                 verbose: bool = True, identity_aggregation: Optional[str] = None, identity_k: int = 3):
+        """``identity_aggregation`` ('max' / 'mean' / 'topk'; ``identity_k`` is the top-k mean's k) makes
+        every match score each student over all of its stored embeddings, as the evaluation notebook's
+        ``identify_probe`` does, in place of the one template per student (None, the default):
+        ``similarity_threshold`` then applies to that identity score.  (``aggregation_method`` is the
+        reference's name for the track vote.)"""
+        check_identity_aggregation(identity_aggregation, identity_k)
+        self.identity_aggregation = identity_aggregation
+        self.identity_k = int(identity_k)
         self.similarity_threshold = similarity_threshold
         self.aggregation_method = aggregation_method
         self.model_type = model_type
@@ -85,7 +93,16 @@ class FaceMatcher:
         if self.verbose:
             print(*args, **kw)
 
+    def _embed_match(self, rgb: torch.Tensor):
+        """The ``launch`` of ``GalleryManager.match_resolved``: one library call from crops to top-k."""
+        agg, agg_k = self.identity_aggregation, self.identity_k
+        if agg is None:
+            return lambda h, k, idx, score: h.embed_match(rgb, k, idx, score)
+        return lambda h, k, idx, score: h.embed_match_identities(rgb, agg, agg_k, k, idx, score)
+
     def match_single_face(self, face_image: np.ndarray, top_k: int = 5) -> List[Tuple[str, str, float]]:
+        if self.identity_aggregation is not None:
+            return self.match_faces([face_image], top_k=top_k)[0]
         embedding = self.embedder.extract_embedding(face_image, normalize=True)
         return self.gallery.search(embedding, top_k=top_k)
 
@@ -94,8 +111,8 @@ class FaceMatcher:
         if len(face_images) == 0:
             return []
         rgb = self.embedder.to_device_crops(list(face_images))  # validates; resizes non-112 crops
-        return self.gallery.match_resolved(len(face_images), top_k,
-                                           lambda h, k, idx, score: h.embed_match(rgb, k, idx, score))
+        return self.gallery.match_resolved(len(face_images), top_k, self._embed_match(rgb),
+                                           self.identity_aggregation, self.identity_k)
 
     # -- tracks ----------------------------------------------------------------
     def _vote(self, frame_matches: List[Dict]):
@@ -154,8 +171,10 @@ class FaceMatcher:
                                              MIN_FRAMES, thr)
             return rec_i.cpu().numpy(), rec_d.cpu().numpy(), idx[:n_rows, 0].cpu().numpy()
 
-        matches, dev = self.gallery.match_resolved_with(
-            len(frames), top_k, lambda h, k, idx, score: h.embed_match(rgb, k, idx, score), consensus)
+        # (with identity_aggregation idx holds identity indices, one per student like the template
+        # rows, so the vote and the id resolution read them the same way)
+        matches, dev = self.gallery.match_resolved_with(len(frames), top_k, self._embed_match(rgb), consensus,
+                                                        self.identity_aggregation, self.identity_k)
         if not matches or not matches[0]:  # empty gallery (or top_k selecting nothing): no valid matches
             return out
         for j, t in enumerate(order):

@@ -247,6 +247,20 @@ def _slice_len(n: int, top_k: int) -> int:
     return len(range(n)[:top_k])
 
 
+IDENTITY_AGGREGATIONS = ("max", "mean", "topk")  # evaluate_models.AGGREGATIONS
+SAMPLE_MAX_ROWS = 1024  # FR_EVAL_MAX_ROWS: stored embeddings of one student in the sample gallery
+
+
+def check_identity_aggregation(aggregation: Optional[str], k: int) -> None:
+    """``aggregation`` is None (template matching) or one of IDENTITY_AGGREGATIONS with ``k >= 1``."""
+    if aggregation is None:
+        return
+    if aggregation not in IDENTITY_AGGREGATIONS:
+        raise ValueError(f"aggregation must be None or one of {list(IDENTITY_AGGREGATIONS)}, got {aggregation!r}")
+    if int(k) < 1:
+        raise ValueError("the top-k mean's k must be >= 1")
+
+
 MAX_PENDING_OPS = 256  # beyond this a full upload is cheaper than replaying row ops
 OP_PUT, OP_DELETE = 0, 1
 
@@ -339,6 +353,8 @@ class GalleryManager:
         self._ids: List[str] = []  # row order of the HBM copy
         self._uid = uuid.uuid4().hex
         self._pending: Optional[List[Tuple[int, str]]] = None  # row ops since the HBM copy; None = full
+        self._sample_pack = None          # (version, rows, offsets, ids): every student's embeddings, packed
+        self._sample_ids: List[str] = []  # identity order of the handle's sample gallery
         # one lock per manager: mutations, the HBM sync and each search's row -> id resolution
         # are atomic with respect to each other (the reference server shares one GalleryManager
         # across Flask request threads, face_recognition_server.py:1102)
@@ -437,42 +453,111 @@ class GalleryManager:
             return np.vstack([self.students[s].template_embedding for s in ids]), ids
 
     # -- matching (device) ---------------------------------------------------
-    def search(self, query_embedding: np.ndarray, top_k: int = 5) -> List[Tuple[str, str, float]]:
-        return self.search_batch(np.asarray(query_embedding).reshape(1, -1), top_k)[0]
+    def search(self, query_embedding: np.ndarray, top_k: int = 5, aggregation: Optional[str] = None,
+               k: int = 3) -> List[Tuple[str, str, float]]:
+        return self.search_batch(np.asarray(query_embedding).reshape(1, -1), top_k, aggregation, k)[0]
 
-    def search_batch(self, queries: np.ndarray, top_k: int = 5) -> List[List[Tuple[str, str, float]]]:
-        """search() for every row of ``queries`` [n, 512], one device round trip."""
+    def search_batch(self, queries: np.ndarray, top_k: int = 5, aggregation: Optional[str] = None,
+                     k: int = 3) -> List[List[Tuple[str, str, float]]]:
+        """search() for every row of ``queries`` [n, 512], one device round trip.
+
+        ``aggregation=None`` scores each student's template.  'max' / 'mean' / 'topk' score every
+        student over all of its stored ``embeddings`` the way the evaluation notebook's
+        ``identify_probe`` does (``k`` is the top-k mean's k), so the configuration an evaluation
+        recommends is the one served: the results are ``(student_id, name, identity score)``."""
+        check_identity_aggregation(aggregation, k)
+        if aggregation is None:
+            q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(self.device)
+            return self.match_resolved(len(queries), top_k, lambda h, kk, idx, score: h.match(q, kk, idx, score))
+        with self._lock:
+            self._packed_samples()  # refuses an over-long student before anything touches the device
         q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(self.device)
-        return self.match_resolved(len(queries), top_k, lambda h, k, idx, score: h.match(q, k, idx, score))
+        return self.match_resolved(len(queries), top_k,
+                                   lambda h, kk, idx, score: h.match_identities(q, aggregation, k, kk, idx, score),
+                                   aggregation, k)
 
-    def match_resolved(self, n: int, top_k: int, launch) -> List[List[Tuple[str, str, float]]]:
+    def match_resolved(self, n: int, top_k: int, launch, aggregation: Optional[str] = None,
+                       agg_k: int = 3) -> List[List[Tuple[str, str, float]]]:
         """Bring the HBM copy up to date, run ``launch(handle, k, idx, score)`` (any kernel
         sequence that fills idx/score [n,k] with gallery rows), and turn rows into
         ``(sid, name, score)`` -- all under the gallery lock, so a concurrent mutation can
         neither change the rows between the match and their resolution nor make two threads
-        replay one delta twice."""
-        return self.match_resolved_with(n, top_k, launch, None)[0]
+        replay one delta twice.  With ``aggregation`` the copy brought up to date is the sample
+        gallery and ``launch`` fills idx with identity indices (``Handle.match_identities`` /
+        ``embed_match_identities``)."""
+        return self.match_resolved_with(n, top_k, launch, None, aggregation, agg_k)[0]
 
-    def match_resolved_with(self, n: int, top_k: int, launch, on_device):
+    def match_resolved_with(self, n: int, top_k: int, launch, on_device, aggregation: Optional[str] = None,
+                            agg_k: int = 3):
         """:meth:`match_resolved`, and ``on_device(handle, idx, score)`` on the filled device
         tensors before they are copied out (e.g. the track vote on the resident top-k), under the
         same lock -> ``(results, on_device's return value)``; the value is None when nothing was
         matched (empty gallery, ``top_k`` selecting no row, n == 0) or ``on_device`` is None."""
+        check_identity_aggregation(aggregation, agg_k)
         with self._lock:
             if not self.students:
                 return [[] for _ in range(n)], None
             k = _slice_len(len(self.students), top_k)
             if k == 0 or n == 0:
                 return [[] for _ in range(n)], None
-            h = self._sync_device()
+            h = self._sync_device() if aggregation is None else self._sync_samples_locked()
             idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
             score = torch.empty((n, k), dtype=torch.float32, device=self.device)
             launch(h, k, idx, score)
             extra = on_device(h, idx, score) if on_device is not None else None
             idx, score = idx.cpu().numpy(), score.cpu().numpy()
-            ids = self._ids
+            ids = self._ids if aggregation is None else self._sample_ids
             return [[(ids[i], self.students[ids[i]].name, float(s)) for i, s in zip(ri, rs)]
                     for ri, rs in zip(idx, score)], extra
+
+    def search_identities_device(self, queries: torch.Tensor, k: int, aggregation: str = "topk",
+                                 agg_k: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
+        """:meth:`search_device` over the stored samples: float32 [n,512] on the GPU -> (int32 [n,k]
+        identity indices, float32 [n,k] identity scores).  Identity i is the i-th student in dict order
+        at the time of the call; the same caveat about concurrent mutation applies."""
+        if aggregation is None:
+            raise ValueError(f"aggregation must be one of {list(IDENTITY_AGGREGATIONS)}")
+        check_identity_aggregation(aggregation, agg_k)
+        with self._lock:
+            h = self._sync_samples_locked()
+            n = queries.shape[0]
+            idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+            score = torch.empty((n, k), dtype=torch.float32, device=self.device)
+            h.match_identities(queries.contiguous(), aggregation, agg_k, k, idx, score)
+            return idx, score
+
+    def _packed_samples(self) -> Tuple[np.ndarray, np.ndarray, List[str]]:
+        """(rows float32 [G,512], offsets int32 [S+1], ids) of every student's ``embeddings`` in dict
+        order (the reference's pickles hold float64: cast here), packed once per gallery version."""
+        if self._sample_pack is not None and self._sample_pack[0] == self._version:
+            return self._sample_pack[1:]
+        ids, blocks = [], []
+        for sid, rec in self.students.items():
+            e = np.asarray(rec.embeddings, dtype=np.float32).reshape(-1, 512)
+            if e.shape[0] > SAMPLE_MAX_ROWS:
+                raise NotImplementedError(f"student {sid} has {e.shape[0]} embeddings: identity matching takes at "
+                                          f"most {SAMPLE_MAX_ROWS} per student (aggregation=None matches templates)")
+            if e.shape[0] < 1:
+                raise ValueError(f"student {sid} has no embeddings")
+            ids.append(sid)
+            blocks.append(e)
+        offsets = np.zeros(len(ids) + 1, dtype=np.int32)
+        if ids:
+            offsets[1:] = np.cumsum([b.shape[0] for b in blocks])
+        rows = np.ascontiguousarray(np.concatenate(blocks, axis=0)) if blocks else np.zeros((0, 512), np.float32)
+        self._sample_pack = (self._version, rows, offsets, ids)
+        return rows, offsets, ids
+
+    def _sync_samples_locked(self) -> "_lib.Handle":
+        """The handle with this manager's sample gallery at the current version: a full upload
+        (``fr_samples_set``) whenever the version has moved since the last one."""
+        h = self._get_handle()
+        tag = (self._uid, self._version)
+        if h.samples_tag != tag:
+            rows, offsets, ids = self._packed_samples()
+            h.samples_set(torch.from_numpy(rows).to(self.device), offsets, tag)
+            self._sample_ids = ids
+        return h
 
     def search_device(self, queries: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device form: float32 [n,512] on the GPU -> (int32 [n,k] gallery rows, float32 [n,k] scores).
@@ -763,6 +848,7 @@ class GalleryManager:
     def _touch(self, op: Optional[Tuple[int, str]] = None) -> None:
         """Bump the version; ``op`` = the row op a device delta replays (None: full upload)."""
         self._version += 1
+        self._sample_pack = None
         if op is None or self._pending is None:
             self._pending = None
         else:

@@ -10,6 +10,8 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
     e = torch.ops.frhip.embed(rgb_u8_nhwc, hid, True)        # [N,512] f32
     idx, score = torch.ops.frhip.match_topk(e, hid, 5)       # [N,5] i32 / f32
     idx, score, e = torch.ops.frhip.embed_match(rgb, hid, 5)
+    idx, score = torch.ops.frhip.match_identities(e, hid, "topk", 3, 5)   # identities of the sample gallery
+    idx, score, e = torch.ops.frhip.embed_match_identities(rgb, hid, "topk", 3, 5)
     aug = torch.ops.frhip.augment_faces(crops_u8_nhwc, 8)    # [N,8,H,W,3] u8 (needs no model)
     rec_i, rec_d = torch.ops.frhip.track_consensus(idx, score, offsets, 0.55, 3, 0.5)  # [T,8] i32 / [T,2] f64
     tid, quality, slot, info = torch.ops.frhip.capture_tracks(bbox, metrics, valid, frame_offsets, clip_offsets,
@@ -133,6 +135,44 @@ def embed_match(rgb: torch.Tensor, handle: int, k: int) -> Tuple[torch.Tensor, t
 
 @embed_match.register_fake
 def _(rgb, handle, k):
+    n = rgb.shape[0]
+    return (rgb.new_empty((n, k), dtype=torch.int32), rgb.new_empty((n, k), dtype=torch.float32),
+            rgb.new_empty((n, 512), dtype=torch.float32))
+
+
+@torch.library.custom_op("frhip::match_identities", mutates_args=())
+def match_identities(q: torch.Tensor, handle: int, aggregation: str, agg_k: int,
+                     k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    h = _get(handle)
+    if q.dtype != torch.float32 or q.dim() != 2 or q.shape[1] != 512 or q.device != h.device:
+        raise ValueError("expected a float32 [N,512] query tensor on the handle's device")
+    q = q.contiguous()
+    idx = torch.empty((q.shape[0], k), dtype=torch.int32, device=q.device)
+    score = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
+    h.match_identities(q, aggregation, agg_k, k, idx, score)
+    return idx, score
+
+
+@match_identities.register_fake
+def _(q, handle, aggregation, agg_k, k):
+    return (q.new_empty((q.shape[0], k), dtype=torch.int32), q.new_empty((q.shape[0], k), dtype=torch.float32))
+
+
+@torch.library.custom_op("frhip::embed_match_identities", mutates_args=())
+def embed_match_identities(rgb: torch.Tensor, handle: int, aggregation: str, agg_k: int,
+                           k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    h = _get(handle)
+    rgb = _check_rgb(rgb, h)
+    n = rgb.shape[0]
+    idx = torch.empty((n, k), dtype=torch.int32, device=rgb.device)
+    score = torch.empty((n, k), dtype=torch.float32, device=rgb.device)
+    emb = torch.empty((n, 512), dtype=torch.float32, device=rgb.device)
+    h.embed_match_identities(rgb, aggregation, agg_k, k, idx, score, emb)
+    return idx, score, emb
+
+
+@embed_match_identities.register_fake
+def _(rgb, handle, aggregation, agg_k, k):
     n = rgb.shape[0]
     return (rgb.new_empty((n, k), dtype=torch.int32), rgb.new_empty((n, k), dtype=torch.float32),
             rgb.new_empty((n, 512), dtype=torch.float32))

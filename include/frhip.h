@@ -391,6 +391,54 @@ int fr_eval_probes(fr_handle* h, const float* scores /* device [n][n_ids] */, in
                    int32_t* rec_i /* device [n][4] */, float* rec_f /* device [n][4] */,
                    int64_t* counts /* device [n_thr][4] */, void* stream);
 
+/* Identity matching: serving with the configuration the evaluation recommends.  Where fr_match_topk
+ * scores one template per student, these calls score every identity over all of its enrolled rows,
+ * as identify_probe does (fr_identity_scores' sim and out), against a sample gallery that lives in the
+ * handle beside the template gallery; fr_gallery_* and fr_match_topk neither read nor change it, and
+ * these calls neither read nor change theirs.
+ *
+ * fr_samples_set: E [id_offsets[n_ids]][512] f32 (host, or device with src_is_device), identity i =
+ * rows [id_offsets[i], id_offsets[i+1]) (host offsets, id_offsets[0] = 0, 1..FR_EVAL_MAX_ROWS rows each).
+ * Copies the rows and stages everything a match needs: the offsets, the kernels' tile cuts, every
+ * row's norm (the f32 rounding of the square root of its double sum of squares, as fr_identity_scores
+ * computes it per call) and whether any row is off-unit.  Replaces the previous sample gallery;
+ * n_ids == 0 clears it.  Synchronises -- the only call of the four that does.  Any handle will do.
+ * NULL buffers, n_ids < 0 and offsets fr_identity_scores refuses -> FR_ERR_INVALID_ARGUMENT (checked
+ * before the handle, so also reported for h == NULL); 2^29 rows or more -> FR_ERR_UNSUPPORTED.
+ * fr_samples_size: the identities and rows held (0, 0 without a sample gallery); either may be NULL. */
+int fr_samples_set(fr_handle* h, const float* E, const int32_t* id_offsets /* host [n_ids + 1] */, int n_ids,
+                   int src_is_device, void* stream);
+int fr_samples_size(fr_handle* h, int* n_ids, int* rows);
+
+/* The k best identities of n queries.  Q: device [n][512]; idx / score: device [n][k], idx identity
+ * indices (the order of fr_samples_set's offsets).  The scores of query p are row p of
+ * fr_identity_scores' out for (Q, the sample rows, the offsets, aggregation, agg_k): the notebook's
+ * cosine_similarity 0.01 rule on raw dots, neither side renormalised, then FR_AGG_MAX / _MEAN / _TOPK
+ * (agg_k is the top-k mean's k and ignored by the other two).  The k largest come back in descending
+ * order, equal scores with the LOWER identity index first: Python's stable sorted(..., reverse=True)
+ * over the dict order in identify_probe, the rule of fr_eval_probes' best.  (fr_match_topk ranks the
+ * higher row first.)  Scores must not be NaN.
+ *   small    one query, or n <= 16 queries with n * rows <= 65,536: one fused launch.  A workgroup
+ *            dots one query against one tile of whole identities, applies the 0.01 rule on the
+ *            stored norms and aggregates in LDS; only [n][n_ids] scores reach HBM.  The dots are f32
+ *            fmaf chains in a fixed order, whatever the precision mode.
+ *   larger   fr_identity_scores' launches on the stored offsets, tiles and norms: the score GEMM in
+ *            the handle's precision mode into its workspace (chunks of queries below 2 GiB), the
+ *            aggregation kernel, the top-k.
+ * Both paths aggregate with one loop, so a score depends on nothing but the identity's similarity
+ * values; the two paths' dots differ in summation order (a few f32 ulp).  Asynchronous on stream: no
+ * host synchronise, nothing staged from host memory (workspace may grow on first use).  n == 0 is a
+ * no-op.  No sample gallery -> FR_ERR_STATE.  NULL buffers, n < 0, an unknown aggregation, FR_AGG_TOPK
+ * with agg_k < 1 and k outside [1, n_ids] -> FR_ERR_INVALID_ARGUMENT; FR_AGG_TOPK with agg_k >
+ * FR_EVAL_MAX_K -> FR_ERR_UNSUPPORTED. */
+int fr_match_identities(fr_handle* h, const float* Q /* device [n][512] */, int n, int aggregation, int agg_k, int k,
+                        int32_t* idx /* device [n][k] */, float* score /* device [n][k] */, void* stream);
+/* fr_embed_match with identity matching in place of the template match: the same forward (normalised
+ * embeddings, graph replay and lanes as fr_embed_match runs them, so emb_out is bitwise its emb_out),
+ * then fr_match_identities on the embeddings, on the same stream.  emb_out: device [n][512], or NULL. */
+int fr_embed_match_identities(fr_handle* h, const uint8_t* rgb /* device [n][112][112][3] */, int n, int aggregation,
+                              int agg_k, int k, int32_t* idx, float* score, float* emb_out, void* stream);
+
 /* FaceAligner.align for n faces of one frame (face_recognition.py:50-75): similarity fit of
  * each face's 5 landmarks to the reference template (cv2.estimateAffinePartial2D semantics,
  * host, double) then warpAffine INTER_LINEAR / BORDER_CONSTANT 0 on the device, so the crops

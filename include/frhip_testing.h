@@ -140,6 +140,15 @@ int frt_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val,
  * rule, the most whose [probes][G] score matrix stays below 2 GiB), so a test can put a chunk seam
  * inside a small batch. */
 int frt_set_eval_chunk(int probes);
+/* Process-wide: the path of fr_match_identities / fr_embed_match_identities.  0: the built-in rule
+ * (the fused kernel for one query and for n <= 16 queries with n * rows <= 65,536, else the composed
+ * path); 1: the fused kernel for every n;
+ * 2: the composed path for every n (its GEMM chunks follow frt_set_eval_chunk).  Tests put both
+ * paths on the same inputs. */
+int frt_set_identify_path(int mode);
+/* Process-wide: the row cap of the fused kernel's tiles, read by the next fr_samples_set (1..1024;
+ * 0: the default).  An identity longer than the cap is a tile of its own.  A/B of the tile size. */
+int frt_set_identify_tile_rows(int rows);
 
 /* Detector internals of fr_detect for n <= max_frames frames: letterbox + network only.
  * heads: device f32, the three levels' maps back to back, each [n][H/s][W/s][32] for
