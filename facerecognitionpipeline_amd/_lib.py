@@ -45,6 +45,7 @@ _SIGNATURES = {
     "fr_gallery_read": (_I, [_P, _I, _I, _P, _I, _P]),
     "fr_build_templates": (_I, [_P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P]),
     "fr_track_consensus": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_double, _I, ctypes.c_double, _P, _P, _P]),
+    "fr_photo_rollcall": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_double, _I, _P, _P, _P, _P]),
     "fr_capture_tracks": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_double, _I, ctypes.c_double, _I, _P, _P, _P,
                                _P, _P]),
     "fr_live_tracks": (_I, [_P, _P, _P, _P, _P, _I, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -291,6 +292,32 @@ class Handle:
                                            float(min_quality), int(min_frames), float(similarity_threshold),
                                            ptr(out_i), ptr(out_d), stream_of(self.device)), self.h)
         return out_i, out_d
+
+    def photo_rollcall(self, idx: torch.Tensor, score: torch.Tensor, offsets, similarity_threshold: float = 0.5,
+                       mode: int = 0):
+        """Who is in each photograph (include/frhip.h, fr_photo_rollcall): len(offsets)-1 photographs
+        whose faces are CSR rows (0..1024 each) of the device top-k output ``idx`` int32 / ``score``
+        float32 [total,k]; ``mode`` 0 (FR_ROLLCALL_INDEPENDENT: the reference's top-1 rule per face) or
+        1 (FR_ROLLCALL_EXCLUSIVE: a row goes to at most one face of a photograph) -> (out_face int32
+        [total,4] = status, row, column, 0; out_score float32 [total]; out_image int32 [P,4] = faces,
+        recognized, candidates, displaced) on the device."""
+        if (idx.dim() != 2 or idx.dtype != torch.int32 or score.dtype != torch.float32
+                or tuple(score.shape) != tuple(idx.shape)):
+            raise ValueError("expected idx int32 [total,k] and score float32 [total,k]")
+        self._require_device("idx / score", idx, score)
+        off, P = _csr_offsets(offsets)
+        if P < 0 or int(off[-1]) != idx.shape[0]:  # also without photographs
+            raise ValueError(f"offsets must end at the {idx.shape[0]} rows of idx / score")
+        idx, score = idx.contiguous(), score.contiguous()
+        total = idx.shape[0]
+        out_face = torch.empty((total, 4), dtype=torch.int32, device=self.device)
+        out_score = torch.empty((total,), dtype=torch.float32, device=self.device)
+        out_image = torch.empty((P, 4), dtype=torch.int32, device=self.device)
+        check(self._lib.fr_photo_rollcall(self.h, ptr(idx) if total else None, ptr(score) if total else None,
+                                          idx.shape[1], off.ctypes.data, P, float(similarity_threshold), int(mode),
+                                          ptr(out_face) if total else None, ptr(out_score) if total else None,
+                                          ptr(out_image), stream_of(self.device)), self.h)
+        return out_face, out_score, out_image
 
     def capture_tracks(self, bbox: torch.Tensor, metrics: torch.Tensor, valid: torch.Tensor, frame_offsets,
                        clip_offsets=None, max_disappeared: int = 30, max_distance: float = 50,

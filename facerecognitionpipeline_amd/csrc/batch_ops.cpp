@@ -1,5 +1,5 @@
 // libfrhip public C API (include/frhip.h), the calls over CSR batches: fr_build_templates,
-// fr_track_consensus, fr_capture_tracks, fr_live_tracks, fr_server_tracks, fr_identity_scores and
+// fr_track_consensus, fr_photo_rollcall, fr_capture_tracks, fr_live_tracks, fr_server_tracks, fr_identity_scores and
 // fr_eval_probes.
 // They share one shape: lock_handle; the argument checks, which need no handle and so report the
 // same way for h == NULL (csr_check for the offsets); "NULL handle"; the offsets staged with
@@ -155,6 +155,33 @@ int fr_track_consensus(fr_handle* h, const int32_t* idx, const float* score, int
   const hipError_t e = launch_track_consensus(idx, score, k, d_off, n_tracks, min_quality, min_frames,
                                               similarity_threshold, out_i, out_d, s);
   if (e != hipSuccess) return launch_fail(h, "track consensus", e);
+  FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
+  return FR_OK;
+}
+
+int fr_photo_rollcall(fr_handle* h, const int32_t* idx, const float* score, int k, const int32_t* offsets,
+                      int n_images, double similarity_threshold, int mode, int32_t* out_face, float* out_score,
+                      int32_t* out_image, void* stream) {
+  auto lk = lock_handle(h);
+  if (n_images < 0 || (n_images > 0 && (!offsets || !out_image)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n_images or NULL buffer");
+  if (k < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "k must be >= 1");
+  if (mode != FR_ROLLCALL_INDEPENDENT && mode != FR_ROLLCALL_EXCLUSIVE)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "mode must be FR_ROLLCALL_INDEPENDENT or _EXCLUSIVE");
+  // photographs of any number of faces up to the cap, also none
+  const std::string bad = csr_check(offsets, n_images, 0, ROLLCALL_MAX_FACES, {"offsets", "photograph", "faces"});
+  if (!bad.empty()) return fail(h, FR_ERR_INVALID_ARGUMENT, bad);
+  if (n_images > 0 && offsets[n_images] > 0 && (!idx || !score || !out_face || !out_score))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL buffer");
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  if (n_images == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int* d_off;
+  if (int rc = stage_int32(h, s, {{offsets, (size_t)n_images + 1}}, &d_off)) return rc;
+  const hipError_t e = launch_photo_rollcall(idx, score, k, d_off, n_images, similarity_threshold, mode, out_face,
+                                             out_score, out_image, s);
+  if (e != hipSuccess) return launch_fail(h, "photo rollcall", e);
   FR_HIP(h, hipStreamSynchronize(s));  // the offsets were staged from pageable host memory
   return FR_OK;
 }

@@ -1,5 +1,5 @@
 // Reductions over one workgroup of 256 threads (4 waves of 64), shared by track.hip, capture.hip,
-// live.hip, gallery.hip, evaluate.hip and embed_misc.hip.
+// live.hip, gallery.hip, evaluate.hip, embed_misc.hip and rollcall.hip.
 //
 // The contract of every block_* function here, for all 256 threads of the block calling it:
 //   - a barrier comes before the write of `red` (4 elements of LDS), so LDS written before the
@@ -46,6 +46,20 @@ __device__ __forceinline__ int block_max(int v, int* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+// Maximum of unsigned 64-bit keys (rollcall.hip: a score's ordered image over a face index).
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off, 64);
+    v = o > v ? o : v;
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const unsigned long long a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
+  return a > b ? a : b;
 }
 
 // Sum of double, the wave partials in sequence: ((r0 + r1) + r2) + r3.

@@ -284,6 +284,18 @@ hipError_t launch_track_consensus(const int* idx, const float* score, int k, con
                                   double min_quality, int min_frames, double similarity_threshold, int* out_i,
                                   double* out_d, hipStream_t s);
 
+// Photograph roll call (rollcall.hip: FaceMatcher.match_single_image's decision, and its exclusive
+// form) of n_images CSR slices of the top-k output idx / score [total][k]; offsets: device
+// [n_images + 1], 0..ROLLCALL_MAX_FACES faces each; out_face: [total][4] = status, row, column, 0;
+// out_score: [total] = the reported score; out_image: [n_images][4] = faces, recognized, candidates,
+// displaced.
+constexpr int ROLLCALL_MAX_FACES = 1024;
+enum RollcallMode : int { ROLLCALL_INDEPENDENT = 0, ROLLCALL_EXCLUSIVE = 1 };
+enum FaceStatus : int { FACE_RECOGNIZED = 0, FACE_CANDIDATE = 1, FACE_DISPLACED = 2 };
+hipError_t launch_photo_rollcall(const int* idx, const float* score, int k, const int* offsets, int n_images,
+                                 double similarity_threshold, int mode, int* out_face, float* out_score,
+                                 int* out_image, hipStream_t s);
+
 // Capture sessions (capture.hip: SimpleTracker.update + FrameAccumulator) of n_clips CSR slices: clip c
 // = frames [clip_off[c], clip_off[c+1]), frame f = detections [frame_off[f], frame_off[f+1]) of bbox
 // [total][4] / metrics [total][5] / valid [total]; both offset arrays on the device, at most

@@ -12,15 +12,24 @@ decides every track in one ``fr_track_consensus`` launch on the top-k output whi
 in HBM; ``_aggregate_matches`` / ``_get_best_candidate`` are the host statement of the same
 vote (and serve tracks longer than the kernel's 1024 frames).
 
-Out of scope: ``match_single_image`` (needs a loaded detector; ``FaceProcessor`` +
-``match_faces`` cover it), ``_save_match_visualization`` (cv2 drawing) and the CLI ``main``.
+The photograph flow (:148-319, ``--single_image``) is ``match_single_image`` and its batched form
+``match_images``: detect, align and blur over all photographs in one pass, the crops gathered into
+result order on the device, one embed + match launch, and every face decided by
+``fr_photo_rollcall`` on the resident top-k output (``photo_rollcall_host`` is the host statement
+of that rule).  ``exclusive=True`` is not in the reference: a student is then given to at most one
+face of a photograph.  ``_save_match_visualization`` keeps the reference's path rule and colours and
+draws with PIL, and ``main`` takes the reference's arguments.
+
+Out of scope: ``visualize_detections`` (matplotlib).
 """
 from __future__ import annotations
 
+import argparse
 import json
 import os
 from collections import Counter
 from datetime import datetime
+from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -35,6 +44,61 @@ TRACK_MAX_FRAMES = 1024
 TRACK_STATUS_NAMES = ("recognized", "few_frames", "no_consensus", "below_threshold")
 MIN_QUALITY = 0.55  # face_matcher.py:324 / :366
 MIN_FRAMES = 3      # face_matcher.py:325
+# include/frhip.h FR_ROLLCALL_* / FR_FACE_*
+ROLLCALL_INDEPENDENT, ROLLCALL_EXCLUSIVE = 0, 1
+FACE_RECOGNIZED, FACE_CANDIDATE, FACE_DISPLACED = 0, 1, 2
+ROLLCALL_MAX_FACES = 1024
+SCRIPT_DIR = Path(__file__).resolve().parent
+# face_matcher.py:160-174: the processor match_single_image builds
+PHOTO_PROCESSOR_CONFIG = {
+    "output_size": 112, "det_size": (640, 640), "det_thresh": 0.5,
+    "quality_filter_config": {"min_det_score": 0.5, "min_face_size": 40, "max_yaw": 60, "max_pitch": 45,
+                              "max_roll": 45, "check_blur": True, "blur_threshold": 50},
+    "providers": ["CUDAExecutionProvider", "CPUExecutionProvider"],
+}
+
+
+def photo_rollcall_host(idx, score, offsets, similarity_threshold: float = 0.5, mode: int = ROLLCALL_INDEPENDENT):
+    """What ``fr_photo_rollcall`` computes (include/frhip.h), stated as a sort and a scan: ``idx`` int32
+    / ``score`` float32 [total,k] top-k rows, photograph p = faces [offsets[p], offsets[p+1]) (any
+    number of faces) -> (out_face int32 [total,4] = status, row, column, 0; out_score float32 [total];
+    out_image int32 [P,4] = faces, recognized, candidates, displaced)."""
+    if mode not in (ROLLCALL_INDEPENDENT, ROLLCALL_EXCLUSIVE):
+        raise ValueError("mode must be ROLLCALL_INDEPENDENT or ROLLCALL_EXCLUSIVE")
+    idx = np.asarray(idx, np.int32)
+    score = np.asarray(score, np.float32)
+    offsets = np.asarray(offsets, np.int64).reshape(-1)
+    total = idx.shape[0]
+    out_face = np.zeros((total, 4), np.int32)
+    out_score = np.zeros(total, np.float32)
+    out_image = np.zeros((len(offsets) - 1, 4), np.int32)
+    with np.errstate(invalid="ignore"):
+        claim = score.astype(np.float64) >= float(similarity_threshold)  # never true for a NaN
+    for p, (lo, hi) in enumerate(zip(offsets[:-1], offsets[1:])):
+        granted: Dict[int, int] = {}  # face -> column
+        if mode == ROLLCALL_EXCLUSIVE:
+            f, c = np.nonzero(claim[lo:hi])
+            s = score[lo:hi][f, c]
+            held = set()
+            # score descending (as f32 values), then face, then column ascending
+            for j in np.lexsort((c, f, -s)):
+                face, row = int(f[j]), int(idx[lo + f[j], c[j]])
+                if face not in granted and row not in held:
+                    granted[face] = int(c[j])
+                    held.add(row)
+        for face in range(int(hi - lo)):
+            at = int(lo) + face
+            if mode == ROLLCALL_EXCLUSIVE:
+                col = granted.get(face, 0)
+                status = (FACE_RECOGNIZED if face in granted else
+                          FACE_DISPLACED if claim[at, 0] else FACE_CANDIDATE)
+            else:
+                col, status = 0, (FACE_RECOGNIZED if claim[at, 0] else FACE_CANDIDATE)
+            out_face[at] = (status, idx[at, col], col, 0)
+            out_score[at] = score[at, col]
+            out_image[p, 1 + status] += 1
+        out_image[p, 0] = hi - lo
+    return out_face, out_score, out_image
 
 
 def track_consensus_host(keys: Sequence, scores: Sequence[float], min_quality: float = MIN_QUALITY,
@@ -113,6 +177,205 @@ class FaceMatcher:
         rgb = self.embedder.to_device_crops(list(face_images))  # validates; resizes non-112 crops
         return self.gallery.match_resolved(len(face_images), top_k, self._embed_match(rgb),
                                            self.identity_aggregation, self.identity_k)
+
+    # -- photographs -----------------------------------------------------------
+    processor = None  # the FaceProcessor of match_single_image / match_images, kept between calls
+
+    def _photo_processor(self):
+        if self.processor is None:
+            from .face_recognition import FaceProcessor
+            self.processor = FaceProcessor(**PHOTO_PROCESSOR_CONFIG, device=self.embedder.device)
+        return self.processor
+
+    def match_single_image(self, image_path: str, top_k: int = 5, save_visualization: bool = True,
+                           processor=None, exclusive: bool = False) -> Dict:
+        """face_matcher.py:148-271: every face of the photograph at ``image_path`` (``return_all``: the
+        quality gate is reported, not applied) against the gallery -> the reference's dict.
+        ``processor`` replaces the ``FaceProcessor`` of the reference's configuration (built on first
+        use otherwise) and is kept for later calls.  ``exclusive``: see :meth:`match_images`, of which
+        this is the one-path case."""
+        if processor is not None:
+            self.processor = processor
+        if not os.path.exists(image_path):
+            self._print(f"\n{'=' * 60}")
+            self._print(f"MATCHING IMAGE: {image_path}")
+            self._print(f"{'=' * 60}")
+            raise ValueError(f"Image not found: {image_path}")
+        return self.match_images([image_path], top_k=top_k, exclusive=exclusive,
+                                 save_visualization=save_visualization)[0]
+
+    def match_images(self, images, top_k: int = 5, exclusive: bool = False, save_visualization: bool = False,
+                     errors: str = "raise") -> List:
+        """``match_single_image`` for a sequence of photographs of different sizes -- paths or arrays,
+        as ``FaceProcessor.process_images`` takes them (and its ``errors``) -- in one pass: one detect
+        call, one align launch at the processor's size and one blur call over all photographs; the
+        crops stay on the device, are gathered there into result order (``process_numpy``'s: det_score
+        x blur_score descending, which ``face_index`` counts) and go through one ``embed_match`` /
+        ``embed_match_identities`` launch; ``fr_photo_rollcall`` decides every face on the top-k output
+        before it is copied out.  Returns one ``match_single_image`` dict per item (``image_path`` is
+        None for an array; an array is not visualised).
+
+        ``exclusive=False`` is the reference's rule: a face is recognised if its top-1 score reaches
+        the threshold, so two faces of a photograph may both come out as one student.
+        ``exclusive=True`` lets a student be held by one face of a photograph only (the rule of
+        ``fr_photo_rollcall``'s FR_ROLLCALL_EXCLUSIVE): a recognised face also carries ``match_rank``,
+        the 1-based rank among its ``top_matches`` that it was given, and a face that lost its top-1 and
+        every other match above the threshold has ``recognized: False``, its top-1 as
+        ``best_candidate`` and ``reason: 'claimed_by_other_face'``."""
+        processor = self._photo_processor()
+        out, items, faces, crops, blur = processor._detect_align_images(images, errors)
+        per_image, order, at = [], [], 0
+        for (_slot, _image), fs in zip(items, faces):
+            # the gate, sort and dicts of process_numpy, with a crop's position in place of the crop
+            res = processor._gate(fs, np.arange(at, at + len(fs)), None if blur is None else blur[at:at + len(fs)],
+                                  True) if fs else []
+            per_image.append(res)
+            order.extend(int(r["aligned_face"]) for r in res)
+            at += len(fs)
+        n = len(order)
+        offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_image])]).astype(np.int64)
+        thr = float(self.similarity_threshold)
+        mode = ROLLCALL_EXCLUSIVE if exclusive else ROLLCALL_INDEPENDENT
+        matches, decided = [], None
+        if n:
+            rgb = crops.to(self.embedder.device)
+            if order != list(range(n)):
+                rgb = rgb[torch.as_tensor(order, dtype=torch.int64, device=rgb.device)]
+            if tuple(rgb.shape[1:3]) != (112, 112):  # a processor of another output_size
+                resized = torch.empty((n, 112, 112, 3), dtype=torch.uint8, device=rgb.device)
+                self.embedder.model.resize_crops(rgb.contiguous(), resized)
+                rgb = resized
+            rgb = rgb.contiguous()
+            on_device = max(len(r) for r in per_image) <= ROLLCALL_MAX_FACES
+
+            def rollcall(h, idx, score):
+                if not on_device:
+                    return None
+                face, fscore, _image = h.photo_rollcall(idx, score, offsets, thr, mode)
+                return face.cpu().numpy(), fscore.cpu().numpy()
+
+            matches, decided = self.gallery.match_resolved_with(n, top_k, self._embed_match(rgb), rollcall,
+                                                                self.identity_aggregation, self.identity_k)
+            if decided is None and matches and matches[0]:
+                # a photograph past the kernel's 1024 faces: the host statement, a student's id as its row
+                key: Dict[str, int] = {}
+                rows = np.array([[key.setdefault(sid, len(key)) for sid, _n, _s in m] for m in matches], np.int32)
+                scores = np.array([[s for _sid, _n, s in m] for m in matches], np.float32)
+                decided = photo_rollcall_host(rows, scores, offsets, thr, mode)[:2]
+        for j, ((slot, _image), res) in enumerate(zip(items, per_image)):
+            item = images[slot]
+            path = os.fspath(item) if isinstance(item, (str, bytes)) or hasattr(item, "__fspath__") else None
+            lo = int(offsets[j])
+            out[slot] = self._photo_result(path, res, matches[lo:lo + len(res)],
+                                           None if decided is None else decided[0][lo:lo + len(res)],
+                                           top_k, exclusive, save_visualization and path is not None)
+        return out
+
+    def _photo_result(self, image_path, faces: List[Dict], results: List, decided, top_k: int, exclusive: bool,
+                      save_visualization: bool) -> Dict:
+        """The dict and the printing of face_matcher.py:152-271 for one photograph: ``faces`` in
+        result order, ``results[i]`` the resolved top-k of face i, ``decided[i]`` its roll-call record
+        (status, row, column, 0)."""
+        self._print(f"\n{'=' * 60}")
+        self._print(f"MATCHING IMAGE: {image_path}")
+        self._print(f"{'=' * 60}")
+        if len(faces) == 0:
+            self._print("No faces detected in image")
+            return {"image_path": image_path, "num_faces": 0, "matches": [], "timestamp": datetime.now().isoformat()}
+        self._print(f"Detected {len(faces)} face(s)")
+        matches = []
+        for i, (face, res) in enumerate(zip(faces, results)):
+            self._print(f"\nFace {i + 1}:")
+            self._print(f"  Detection score: {face['det_score']:.3f}")
+            self._print(f"  Valid: {face['is_valid']}")
+            if face["quality_metrics"].get("blur_score"):
+                self._print(f"  Blur score: {face['quality_metrics']['blur_score']:.0f}")
+            if len(res) == 0:
+                self._print("  No matches found in gallery")
+                matches.append({"face_index": i, "bbox": face["bbox"].tolist(), "recognized": False,
+                                "reason": "no_gallery_matches", "quality_metrics": face["quality_metrics"]})
+                continue
+            status, _row, col, _pad = (int(v) for v in decided[i])
+            recognized = status == FACE_RECOGNIZED
+            student_id, name, score = res[col]
+            if recognized:
+                self._print(f"  ✓ Recognized: {name} ({student_id}) - confidence: {score:.3f}")
+            elif status == FACE_DISPLACED:
+                self._print(f"  ⚠ Claimed by another face: {name} ({student_id}) - confidence: {score:.3f}")
+            else:
+                self._print(f"  ⚠ Below threshold: {name} ({student_id}) - confidence: {score:.3f} "
+                            f"(threshold: {self.similarity_threshold})")
+            m = {"face_index": i, "bbox": face["bbox"].tolist(), "recognized": recognized,
+                 "confidence": float(score), "quality_metrics": face["quality_metrics"],
+                 "top_matches": [{"student_id": sid, "name": n, "score": float(s), "rank": rank + 1}
+                                 for rank, (sid, n, s) in enumerate(res)]}
+            if recognized:
+                m["student_id"] = student_id
+                m["name"] = name
+                if exclusive:
+                    m["match_rank"] = col + 1
+            else:
+                m["best_candidate"] = {"student_id": student_id, "name": name, "confidence": float(score)}
+                if status == FACE_DISPLACED:
+                    m["reason"] = "claimed_by_other_face"
+            matches.append(m)
+            self._print(f"  Top {min(top_k, len(res))} matches:")
+            for rank, (sid, n, s) in enumerate(res[:top_k], 1):
+                marker = "→" if rank == 1 else " "
+                self._print(f"    {marker} {rank}. {n} ({sid}): {s:.3f}")
+        if save_visualization:
+            output_path = self._save_match_visualization(image_path, faces, matches)
+            self._print(f"\nVisualization saved to: {output_path}")
+        result = {"image_path": image_path, "num_faces": len(faces),
+                  "num_recognized": sum(1 for m in matches if m.get("recognized", False)), "matches": matches,
+                  "threshold": self.similarity_threshold, "timestamp": datetime.now().isoformat()}
+        self._print(f"\n{'=' * 60}")
+        self._print(f"Summary: {result['num_recognized']}/{result['num_faces']} faces recognized")
+        self._print(f"{'=' * 60}\n")
+        return result
+
+    def _save_match_visualization(self, image_path: str, faces: List[Dict], matches: List[Dict]) -> str:
+        """face_matcher.py:273-319: a box and two label lines per face -- green for a recognised face,
+        (255, 165, 0) for a candidate, red otherwise -- written to
+        ``<gallery stem>_match_results/matched_<filename>`` beside the image.  Drawn with PIL (cv2 is
+        not a dependency): the path, the colours, the 3 px box and the label's place above it are the
+        reference's; the glyphs are PIL's default font, not cv2's Hershey text, so pixel parity of the
+        labels is not pinned."""
+        from PIL import Image, ImageDraw, ImageFont
+        from .face_recognition import load_image_rgb
+        rgb = load_image_rgb(image_path)
+        if rgb is None:
+            raise ValueError(f"Could not load image: {image_path}")
+        image = Image.fromarray(rgb, "RGB")
+        draw = ImageDraw.Draw(image)
+        font = ImageFont.load_default(size=22)  # about FONT_HERSHEY_SIMPLEX at scale 0.8
+        for face, match in zip(faces, matches):
+            x1, y1, x2, y2 = (int(v) for v in face["bbox"])
+            if match.get("recognized", False):
+                color = (0, 255, 0)
+                label = f"{match['name']}\n{match['confidence']:.3f}"
+            elif "best_candidate" in match:
+                color = (255, 165, 0)
+                cand = match["best_candidate"]
+                label = f"{cand['name']}?\n{cand['confidence']:.3f}"
+            else:
+                color = (255, 0, 0)
+                label = "Unknown"
+            # cv2.rectangle's thickness 3 is centred on the box: one pixel to either side
+            draw.rectangle([min(x1, x2) - 1, min(y1, y2) - 1, max(x1, x2) + 1, max(y1, y2) + 1], outline=color, width=3)
+            y_offset = y1 - 10
+            for line in reversed(label.split("\n")):
+                left, top, right, bottom = draw.textbbox((0, 0), line, font=font)
+                w, h = right - left, bottom - top
+                y_offset -= h + 5
+                draw.rectangle([x1, y_offset, x1 + w, y_offset + h + 5], fill=color)
+                draw.text((x1 - left, y_offset - top + 2), line, fill=(0, 0, 0), font=font)
+        gallery_name = Path(self.gallery.gallery_path).stem
+        output_dir = os.path.join(os.path.dirname(image_path), f"{gallery_name}_match_results")
+        os.makedirs(output_dir, exist_ok=True)
+        output_path = os.path.join(output_dir, f"matched_{os.path.basename(image_path)}")
+        image.save(output_path)
+        return output_path
 
     # -- tracks ----------------------------------------------------------------
     def _vote(self, frame_matches: List[Dict]):
@@ -347,3 +610,36 @@ class FaceMatcher:
                 self._print(f"  • {candidate['name']}: confidence {candidate['confidence']:.3f} "
                             f"(needed {self.similarity_threshold})")
         self._print("=" * 60 + "\n")
+
+
+def main(argv: Optional[Sequence[str]] = None):
+    """face_matcher.py:503-589, with the reference's arguments.  ``--single_image`` matches only the
+    image (the reference runs the capture directory first, by mistake)."""
+    parser = argparse.ArgumentParser(description="Match detected faces against student gallery")
+    parser.add_argument("--capture_dir", type=str, default=str(SCRIPT_DIR / "output" / "camera_captures"),
+                        help="Directory containing camera capture tracks")
+    parser.add_argument("--gallery_path", type=str, default=str(SCRIPT_DIR / "gallery" / "students.pkl"),
+                        help="Path to student gallery database")
+    parser.add_argument("--threshold", type=float, default=0.35, help="Similarity threshold for positive match (0-1)")
+    parser.add_argument("--aggregation", type=str, default="consensus",
+                        choices=["consensus", "majority_vote", "avg_similarity", "max_similarity"],
+                        help="Method to aggregate multi-frame matches")
+    parser.add_argument("--no_save", action="store_true", help="Do not save recognition results to files")
+    parser.add_argument("--single_image", type=str, default=None,
+                        help="Path to single image to match (instead of processing capture directory)")
+    parser.add_argument("--top_k", type=int, default=5, help="Number of top matches to show per face")
+    parser.add_argument("--model_type", type=str, default="adaface", choices=["adaface", "arcface"],
+                        help="Type of face recognition model to use")
+    parser.add_argument("--architecture", type=str, default="ir_101", choices=["ir_50", "ir_101"],
+                        help="Model architecture (ir_50 or ir_101)")
+    args = parser.parse_args(argv)
+    matcher = FaceMatcher(gallery_path=args.gallery_path, similarity_threshold=args.threshold,
+                          aggregation_method=args.aggregation, model_type=args.model_type,
+                          architecture=args.architecture)
+    if args.single_image:
+        return matcher.match_single_image(image_path=args.single_image, top_k=args.top_k, save_visualization=True)
+    return matcher.process_capture_directory(capture_dir=args.capture_dir, save_results=not args.no_save)
+
+
+if __name__ == "__main__":
+    main()

@@ -311,6 +311,24 @@ class FaceProcessor:
         scores are distinct.  On smooth content (a wall, a sky, a tiny image upscaled) neighbouring
         anchors score equal to the last bits, and NMS may then keep a neighbouring box of the same
         score in one path and not the other ("Mixed-size image batches")."""
+        out, items, faces, crops, blur = self._detect_align_images(images, errors)
+        at = 0
+        for (slot, image), fs in zip(items, faces):
+            # to the host image by image: a block per image, as process_numpy's, not one block for the
+            # whole call (hundreds of MB for a chunk of group photographs, freshly paged in every call)
+            mine = crops[at:at + len(fs)].cpu().numpy()
+            if image.ndim == 2:  # a gray image's crops go back 2-D, as in process_numpy
+                mine = np.ascontiguousarray(mine[..., 0])
+            out[slot] = self._gate(fs, mine, None if blur is None else blur[at:at + len(fs)], return_all) if fs else []
+            at += len(fs)
+        return out
+
+    def _detect_align_images(self, images, errors: str):
+        """The GPU pass of ``process_images``: -> (out, items, faces, crops, blur).  ``out`` has one slot
+        per item of ``images``, None or the ValueError of an item that cannot be used; ``items`` the
+        usable ones as (slot, image as process_numpy would get it); ``faces[j]`` the detector's faces of
+        ``items[j]``; ``crops`` uint8 [total,S,S,3] on the device, image by image in face order; ``blur``
+        their float64 blur scores on the host, or None (not checked, or no face)."""
         if errors not in ("raise", "return"):
             raise ValueError('errors must be "raise" or "return"')
         out: List = [None] * len(images)
@@ -340,16 +358,7 @@ class FaceProcessor:
                                                    np.zeros((0, 5, 2), np.float32) for fs in faces])
         blur = (self.quality_filter.compute_blur_scores(crops)
                 if self.quality_filter.check_blur and crops.shape[0] else None)
-        at = 0
-        for (slot, image), fs in zip(items, faces):
-            # to the host image by image: a block per image, as process_numpy's, not one block for the
-            # whole call (hundreds of MB for a chunk of group photographs, freshly paged in every call)
-            mine = crops[at:at + len(fs)].cpu().numpy()
-            if image.ndim == 2:  # a gray image's crops go back 2-D, as in process_numpy
-                mine = np.ascontiguousarray(mine[..., 0])
-            out[slot] = self._gate(fs, mine, None if blur is None else blur[at:at + len(fs)], return_all) if fs else []
-            at += len(fs)
-        return out
+        return out, items, faces, crops, blur
 
     def process_numpy(self, image_rgb: np.ndarray, return_all: bool = False) -> List[Dict]:
         faces = self.detector.detect(image_rgb)

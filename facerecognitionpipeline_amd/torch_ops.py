@@ -14,6 +14,7 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
     idx, score, e = torch.ops.frhip.embed_match_identities(rgb, hid, "topk", 3, 5)
     aug = torch.ops.frhip.augment_faces(crops_u8_nhwc, 8)    # [N,8,H,W,3] u8 (needs no model)
     rec_i, rec_d = torch.ops.frhip.track_consensus(idx, score, offsets, 0.55, 3, 0.5)  # [T,8] i32 / [T,2] f64
+    face, fscore, image = torch.ops.frhip.photo_rollcall(idx, score, offsets, 0.35, 1)  # [N,4] i32, [N] f32, [P,4] i32
     tid, quality, slot, info = torch.ops.frhip.capture_tracks(bbox, metrics, valid, frame_offsets, clip_offsets,
                                                               30, 80.0, 12, 0.5, False)  # [N] x 3, [C,4] i32
     tid, prev, attempt, best, info = torch.ops.frhip.live_tracks(bbox, det_blur, frame_offsets, clip_offsets,
@@ -69,7 +70,7 @@ _utility: Dict[torch.device, "_lib.Handle"] = {}
 
 def utility_handle(device) -> "_lib.Handle":
     """A model-less handle on ``device`` for the entry points that need no weights
-    (``augment_faces``, ``track_consensus``, ``capture_tracks``, ``live_tracks``, ``server_tracks``, ``identity_scores``, ``eval_probes``): one per device, created on first use."""
+    (``augment_faces``, ``track_consensus``, ``photo_rollcall``, ``capture_tracks``, ``live_tracks``, ``server_tracks``, ``identity_scores``, ``eval_probes``): one per device, created on first use."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
@@ -203,6 +204,21 @@ def track_consensus(idx: torch.Tensor, score: torch.Tensor, offsets: List[int], 
 def _(idx, score, offsets, min_quality, min_frames, similarity_threshold):
     t = max(len(offsets) - 1, 0)
     return idx.new_empty((t, 8), dtype=torch.int32), idx.new_empty((t, 2), dtype=torch.float64)
+
+
+@torch.library.custom_op("frhip::photo_rollcall", mutates_args=())
+def photo_rollcall(idx: torch.Tensor, score: torch.Tensor, offsets: List[int], similarity_threshold: float,
+                   mode: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    if idx.device.type != "cuda":
+        raise ValueError(f"idx is on {idx.device}: photo_rollcall runs on a HIP device (no CPU fallback)")
+    return utility_handle(idx.device).photo_rollcall(idx, score, offsets, similarity_threshold, mode)
+
+
+@photo_rollcall.register_fake
+def _(idx, score, offsets, similarity_threshold, mode):
+    n, p = idx.shape[0], max(len(offsets) - 1, 0)
+    return (idx.new_empty((n, 4), dtype=torch.int32), idx.new_empty((n,), dtype=torch.float32),
+            idx.new_empty((p, 4), dtype=torch.int32))
 
 
 @torch.library.custom_op("frhip::capture_tracks", mutates_args=())

@@ -179,6 +179,41 @@ int fr_track_consensus(fr_handle* h, const int32_t* idx, const float* score, int
                        int32_t* out_i /* device [n_tracks][8] */, double* out_d /* device [n_tracks][2] */,
                        void* stream);
 
+/* Photograph roll call: the decision of FaceMatcher.match_single_image (face_matcher.py:148-271) for
+ * every face of n_images photographs in one launch, on the top-k output of fr_match_topk /
+ * fr_embed_match / fr_match_identities while it is on the device.  idx / score: device [total][k]
+ * (k >= 1, rows descending; a gallery row or identity index stands for its student); photograph p =
+ * faces [offsets[p], offsets[p+1]) (host offsets, offsets[0] = 0, 0..FR_ROLLCALL_MAX_FACES faces each).
+ * A claim of a face is a column c with (double)score[f][c] >= similarity_threshold (never a NaN; the
+ * threshold may be negative).
+ *   FR_ROLLCALL_INDEPENDENT  the reference's rule, every face on its column 0 alone:
+ *                            FR_FACE_RECOGNIZED if it is a claim, else FR_FACE_CANDIDATE (the
+ *                            reference's best_candidate)
+ *   FR_ROLLCALL_EXCLUSIVE    a row is held by at most one face of a photograph: all claims (f, c) of
+ *                            the photograph ordered by score descending (as f32 values), then face
+ *                            ascending, then column ascending, are scanned, and a claim is granted if
+ *                            its face holds nothing yet and its row is not held.  A face with a
+ *                            granted claim is FR_FACE_RECOGNIZED with that row, score and column; a
+ *                            face whose column 0 was a claim but which was granted nothing is
+ *                            FR_FACE_DISPLACED, one whose column 0 was no claim FR_FACE_CANDIDATE
+ *                            (both report column 0)
+ * out_face[f] = {status, row, column, 0}; out_score[f] = the reported score, bit for bit;
+ * out_image[p] = {n_faces, recognized, candidates, displaced}.  Comparisons only: exact, and a
+ * photograph's result depends on nothing but its own faces.  Any handle will do, finalised or not.
+ * Synchronises (the offsets are staged from the host).  n_images == 0 is a no-op; NULL buffers,
+ * k < 1, offsets[0] != 0, an over-long photograph and an unknown mode -> FR_ERR_INVALID_ARGUMENT
+ * (checked before the handle, so also reported for h == NULL). */
+#define FR_ROLLCALL_INDEPENDENT 0
+#define FR_ROLLCALL_EXCLUSIVE 1
+#define FR_FACE_RECOGNIZED 0
+#define FR_FACE_CANDIDATE 1
+#define FR_FACE_DISPLACED 2 /* its top-1 row went to another face of the photograph */
+#define FR_ROLLCALL_MAX_FACES 1024
+int fr_photo_rollcall(fr_handle* h, const int32_t* idx, const float* score, int k,
+                      const int32_t* offsets /* host [n_images + 1] */, int n_images, double similarity_threshold,
+                      int mode, int32_t* out_face /* device [total][4] */, float* out_score /* device [total] */,
+                      int32_t* out_image /* device [n_images][4] */, void* stream);
+
 /* Capture sessions: SimpleTracker.update and FrameAccumulator (face_detection.py:11-228) with the
  * is_valid test of CameraFaceCapture.process_frame (:271-283) for n_clips independent sessions
  * (cameras) in one launch.  Each session starts from an empty tracker with next_track_id = 1.
