@@ -66,6 +66,9 @@ _SIGNATURES = {
     "fr_detect": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P]),
     "fr_detect_images": (_I, [_P, _P, _P, _I, ctypes.c_float, _I, _P, _P, _P]),
     "fr_align_images": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "fr_detect_device": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P]),
+    "fr_align_device": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "fr_blur_scores_device": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "fr_set_precision": (_I, [_P, _I]),
     "fr_set_conv_algorithm": (_I, [_P, _I]),
     "fr_set_graph_batch": (_I, [_P, _I]),
@@ -589,6 +592,81 @@ class Handle:
                                   int(max_faces), dets.ctypes.data, counts.ctypes.data, stream_of(self.device)),
               self.h)
         return dets, counts
+
+    # -- the chain with device outputs (asynchronous on the current stream, capturable) ------
+    def _out(self, name: str, t, shape, dtype, zero: bool = False) -> torch.Tensor:
+        """The caller's output tensor ``t`` checked, or a new one."""
+        if t is None:
+            return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} {list(shape)} tensor on {self.device}")
+        return t
+
+    def _frames(self, frames: torch.Tensor) -> torch.Tensor:
+        if (not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4
+                or frames.shape[3] != 3):
+            raise ValueError("expected uint8 [n,H,W,3] RGB frames")
+        self._require_device("frames", frames)
+        return frames.contiguous()
+
+    def detect_device(self, frames: torch.Tensor, det_thresh: float = 0.5, max_faces: int = 256, dets=None,
+                      counts=None):
+        """``detect`` with device outputs and no synchronisation (fr_detect_device): frames uint8
+        [n,H,W,3] on the device -> (dets f32 [n,max_faces,15], counts int32 [n]) on the device; rows
+        i < min(counts[f], max_faces) are ``detect``'s, ``counts[f] == -1`` marks a frame over the
+        4096-candidate limit (where ``detect`` raises).  ``dets`` / ``counts``: tensors to write
+        (for graph capture); new ``dets`` are zero-filled."""
+        frames = self._frames(frames)
+        n, F = frames.shape[0], int(max_faces)
+        dets = self._out("dets", dets, (n, F, 15), torch.float32, zero=True)
+        counts = self._out("counts", counts, (n,), torch.int32)
+        check(self._lib.fr_detect_device(self.h, ptr(frames), n, frames.shape[1], frames.shape[2], float(det_thresh),
+                                         F, ptr(dets) if F else None, ptr(counts), stream_of(self.device)), self.h)
+        return dets, counts
+
+    def align_device(self, frames: torch.Tensor, landmarks: torch.Tensor, counts, out_size: int, out=None,
+                     tforms=None, ok=None):
+        """``align_faces`` for every slot of a batch of frames, landmarks read on the device, no
+        synchronisation (fr_align_device).  frames uint8 [n,H,W,3]; ``landmarks`` float32 on the
+        device, either detection rows [n,F,15] (``detect_device``'s dets, read in place) or
+        [n,F,5,2]; ``counts`` int32 [n] on the device (slots i < min(counts[f], F) are live) or None
+        (all live) -> (crops uint8 [n,F,S,S,3], tforms f64 [n,F,2,3], ok uint8 [n,F]).  A slot with
+        ok == 0 (not live, or a fit the host refuses) has an all-zero crop and a NaN tform."""
+        frames = self._frames(frames)
+        n, S = frames.shape[0], int(out_size)
+        lm = landmarks
+        if (not isinstance(lm, torch.Tensor) or lm.dtype != torch.float32 or lm.dim() not in (3, 4)
+                or lm.shape[0] != n or tuple(lm.shape[2:]) not in ((15,), (5, 2))):
+            raise ValueError(f"landmarks must be float32 [{n},F,15] detection rows or [{n},F,5,2]")
+        self._require_device("landmarks", lm)
+        lm = lm.contiguous()
+        F = lm.shape[1]
+        rows = lm.dim() == 3
+        if counts is not None:
+            if counts.dtype != torch.int32 or tuple(counts.shape) != (n,) or not counts.is_contiguous():
+                raise ValueError(f"counts must be a contiguous int32 [{n}] tensor")
+            self._require_device("counts", counts)
+        out = self._out("out", out, (n, F, S, S, 3), torch.uint8)
+        tforms = self._out("tforms", tforms, (n, F, 2, 3), torch.float64)
+        ok = self._out("ok", ok, (n, F), torch.uint8)
+        lm_ptr = (ptr(lm) + (5 * 4 if rows else 0)) if n * F else None
+        check(self._lib.fr_align_device(self.h, ptr(frames), n, frames.shape[1], frames.shape[2], lm_ptr,
+                                        15 if rows else 10, ptr(counts), F, S, ptr(out), ptr(tforms), ptr(ok),
+                                        stream_of(self.device)), self.h)
+        return out, tforms, ok
+
+    def blur_scores_device(self, crops: torch.Tensor, out=None) -> torch.Tensor:
+        """``blur_scores`` with the float64 [n] result on the device and no synchronisation."""
+        if crops.dtype != torch.uint8 or crops.dim() not in (3, 4):
+            raise ValueError("expected uint8 [n,H,W] or [n,H,W,C] images")
+        self._require_device("crops", crops)
+        crops = crops.contiguous()
+        n = crops.shape[0]
+        c = 1 if crops.dim() == 3 else crops.shape[3]
+        out = self._out("out", out, (n,), torch.float64)
+        check(self._lib.fr_blur_scores_device(self.h, ptr(crops), n, crops.shape[1], crops.shape[2], c, ptr(out),
+                                              stream_of(self.device)), self.h)
+        return out
 
     def _image_list(self, images):
         """A list of uint8 [H,W,3] device tensors -> (contiguous tensors on the handle's device, host

@@ -256,6 +256,23 @@ bool fit_similarity(const float* src_f, const float* dst_f, int n, double M[6]) 
   return true;
 }
 
+// The logarithms update_num_iters takes in fit_similarity's calls for n = 5 (p = 0.99,
+// ep = (5 - g) / 5 for g inliers), with its clamps and its std::log: what the device fit
+// (align_fit.h) gets by value in place of a device log.
+void fit_logs(FitLogs* lg) {
+  const double p = std::min(std::max(0.99, 0.), 1.);
+  lg->log_num = std::log(std::max(1. - p, kDblMin));
+  lg->den_zero = 0;
+  for (int g = 0; g <= 5; ++g) {
+    const double ep = std::min(std::max((double)(5 - g) / 5, 0.), 1.);
+    const double q = 1. - ep;
+    const double denom = 1. - q * q;
+    const bool zero = denom < kDblMin;
+    if (zero) lg->den_zero |= 1 << g;
+    lg->log_den[g] = zero ? 0.0 : std::log(denom);
+  }
+}
+
 void invert_affine(const double Mf[6], double Mi[6]) {
   double m[6];
   memcpy(m, Mf, sizeof(m));

@@ -377,6 +377,13 @@ __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ can
   if (tid == 0) out_count[f] = s_nkeep;
 }
 
+// fr_detect_device's mark of a frame whose candidates overflowed decode's buffer.
+__global__ __launch_bounds__(256) void det_overflow_kernel(const int* __restrict__ raw, int n, int cap,
+                                                           int* __restrict__ counts) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f < n && raw[f] > cap) counts[f] = -1;
+}
+
 hipError_t launch_letterbox(const uint8_t* frames, int n, int H, int W, const int* xtab, const int* ytab, int new_w,
                             int new_h, int simd_end, int dw, int dh, uint8_t* out, hipStream_t s) {
   if (n <= 0) return hipSuccess;
@@ -562,6 +569,12 @@ hipError_t launch_nms(const float* cand, const int* count, int n, int cap, float
   if (n <= 0) return hipSuccess;
   if (cap > DET_MAX_CANDIDATES) return hipErrorInvalidValue;
   hipLaunchKernelGGL(nms_kernel, dim3(n), dim3(1024), 0, s, cand, count, cap, iou_thresh, max_out, out, out_count);
+  return hipGetLastError();
+}
+
+hipError_t launch_det_overflow(const int* raw, int n, int cap, int* counts, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(det_overflow_kernel, dim3((n + 255) / 256), dim3(256), 0, s, raw, n, cap, counts);
   return hipGetLastError();
 }
 

@@ -71,10 +71,21 @@ struct Detector {
   std::vector<char> himgs;
   void* imgs = nullptr;
   size_t imgs_cap = 0;
+  // fr_detect_device: the resize tables of the frame sizes seen, on the device ([new_w + new_h][4]
+  // each), so that a call on a size seen before copies nothing from the host
+  struct SizeTabs {
+    int H, W;
+    int* tab;
+    unsigned long long used;  // last use (LRU clock)
+  };
+  static constexpr size_t SIZE_TABS_MAX = 16;
+  std::vector<SizeTabs> size_tabs;
+  unsigned long long size_clock = 0;
   ~Detector() {
     (void)hipFree(arena);
     (void)hipFree(ws);
     (void)hipFree(imgs);
+    for (auto& t : size_tabs) (void)hipFree(t.tab);
   }
 };
 
@@ -502,6 +513,43 @@ int setup_geometry(fr_handle* h, int height, int width, Geometry& g, hipStream_t
   return FR_OK;
 }
 
+// The same for fr_detect_device: *tabs is the size's own device copy of the tables.  A size seen
+// for the first time allocates it and uploads it with one synchronous copy from a local buffer;
+// after that the call touches no host staging and nothing on the device.  The least recently used
+// of SIZE_TABS_MAX sizes makes room (hipFree waits for the device, so no launch still reads it).
+int setup_geometry_cached(fr_handle* h, int height, int width, Geometry& g, const int** tabs) {
+  Detector* d = h->det;
+  if (!letterbox_size(height, width, d->det_w, d->det_h, g))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "frame too small to letterbox");
+  if (d->row_reduce) row_plan(g.new_h, d->det_h, g);
+  for (auto& t : d->size_tabs)
+    if (t.H == height && t.W == width) {
+      t.used = ++d->size_clock;
+      *tabs = t.tab;
+      return FR_OK;
+    }
+  std::vector<int> host((size_t)(g.new_w + g.new_h) * 4, 0);
+  resize_axis_table(g.new_w, width, host.data());
+  resize_axis_table(g.new_h, height, host.data() + 4 * g.new_w);
+  if (d->size_tabs.size() >= Detector::SIZE_TABS_MAX) {
+    size_t lru = 0;
+    for (size_t i = 1; i < d->size_tabs.size(); ++i)
+      if (d->size_tabs[i].used < d->size_tabs[lru].used) lru = i;
+    FR_HIP(h, hipFree(d->size_tabs[lru].tab));
+    d->size_tabs.erase(d->size_tabs.begin() + lru);
+  }
+  int* dev = nullptr;
+  FR_HIP(h, hipMalloc((void**)&dev, host.size() * sizeof(int)));
+  const hipError_t e = hipMemcpy(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(dev);
+    return fail(h, FR_ERR_HIP, std::string("letterbox tables: ") + hipGetErrorString(e));
+  }
+  d->size_tabs.push_back({height, width, dev, ++d->size_clock});
+  *tabs = dev;
+  return FR_OK;
+}
+
 // One chunk of fr_detect_images: B <= max_frames images of their own sizes (validated by the caller).
 // Stages the images' descriptors, scales and concatenated resize tables in one copy and letterboxes
 // them into d->canvas.  g gets the chunk's row plan: new_h is the largest of the chunk, so the rows
@@ -549,11 +597,13 @@ int letterbox_images(fr_handle* h, const uint8_t* const* images, const int32_t* 
 
 int forward_network(fr_handle* h, int B, const Geometry& g, hipStream_t s);
 
-// Letterbox + network for B <= max_frames frames; head maps land in d->hd[0..2].
-int forward_chunk(fr_handle* h, const uint8_t* fr, int B, int height, int width, const Geometry& g, hipStream_t s) {
+// Letterbox + network for B <= max_frames frames; head maps land in d->hd[0..2].  tabs: the frame
+// size's resize tables on the device (setup_geometry's d->tabs or setup_geometry_cached's).
+int forward_chunk(fr_handle* h, const uint8_t* fr, int B, int height, int width, const Geometry& g, const int* tabs,
+                  hipStream_t s) {
   Detector* d = h->det;
-  const int* xtab = d->tabs;
-  const int* ytab = d->tabs + 4 * g.new_w;
+  const int* xtab = tabs;
+  const int* ytab = tabs + 4 * g.new_w;
   const hipError_t e = launch_letterbox(fr, B, height, width, xtab, ytab, g.new_w, g.new_h, g.simd_end, d->det_w,
                                         d->det_h - g.skip1, d->canvas, s);
   if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("letterbox: ") + hipGetErrorString(e));
@@ -667,18 +717,15 @@ int forward_network(fr_handle* h, int B, const Geometry& g, hipStream_t s) {
 
 namespace {
 
-// decode + NMS of the B head maps in d->hd, then the detections of frames [off, off + B) to the host.
-// Decode divides by scales[b] (device, per frame) or, when scales is NULL, by det_scale.  `what` names
-// a frame in the DET_MAX_CANDIDATES error.  counts[] is the full kept count; rows i < min(counts[f],
-// max_faces) of dets are written, for any max_faces >= 0.  Synchronises.
-int postprocess_chunk(fr_handle* h, int B, int off, float det_scale, const float* scales, const char* what,
-                      float det_thresh, int max_faces, float* dets, int32_t* counts, hipStream_t s) {
+// The device part of the post-processing: decode + NMS of the B head maps in d->hd into out (device
+// [B][max_out][15], rows i < min(out_count[b], max_out) written) and out_count (device [B], the full
+// kept count); d->count keeps the frames' anchors above det_thresh.  Decode divides by scales[b]
+// (device, per frame) or, when scales is NULL, by det_scale.  Asynchronous.
+int postprocess_device(fr_handle* h, int B, float det_scale, const float* scales, float det_thresh, int max_out,
+                       float* out, int* out_count, hipStream_t s) {
   Detector* d = h->det;
   const int DW = d->det_w, DH = d->det_h;
   const int lh[3] = {DH / 8, DH / 16, DH / 32}, lw[3] = {DW / 8, DW / 16, DW / 32};
-  // rows per frame that nms_kernel writes and the host copies: the caller's max_faces (the kernel
-  // counts the detections it has no row for), at least 1 so that the copy is never empty
-  const int fmax = std::max(1, std::min(max_faces, d->dets_cap));
   FR_HIP(h, hipMemsetAsync(d->count, 0, B * sizeof(int), s));
   DetDecodeParams dp{};
   int base = 0;
@@ -698,8 +745,21 @@ int postprocess_chunk(fr_handle* h, int B, int off, float det_scale, const float
   dp.cand = d->cand;
   hipError_t e = launch_decode(dp, B, s);
   if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("decode: ") + hipGetErrorString(e));
-  e = launch_nms(d->cand, d->count, B, DET_MAX_CANDIDATES, 0.4f, fmax, d->dets, d->dets_count, s);
+  e = launch_nms(d->cand, d->count, B, DET_MAX_CANDIDATES, 0.4f, max_out, out, out_count, s);
   if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("nms: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+// postprocess_device into the detector's own buffers, then the detections of frames [off, off + B)
+// to the host.  `what` names a frame in the DET_MAX_CANDIDATES error.  counts[] is the full kept
+// count; rows i < min(counts[f], max_faces) of dets are written, for any max_faces >= 0.  Synchronises.
+int postprocess_chunk(fr_handle* h, int B, int off, float det_scale, const float* scales, const char* what,
+                      float det_thresh, int max_faces, float* dets, int32_t* counts, hipStream_t s) {
+  Detector* d = h->det;
+  // rows per frame that nms_kernel writes and the host copies: the caller's max_faces (the kernel
+  // counts the detections it has no row for), at least 1 so that the copy is never empty
+  const int fmax = std::max(1, std::min(max_faces, d->dets_cap));
+  if (int rc = postprocess_device(h, B, det_scale, scales, det_thresh, fmax, d->dets, d->dets_count, s)) return rc;
   std::vector<float> hbuf((size_t)B * fmax * 15);
   std::vector<int> hcnt(B), hraw(B);
   FR_HIP(h, hipMemcpyAsync(hbuf.data(), d->dets, hbuf.size() * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -750,10 +810,31 @@ int detector_run(fr_handle* h, const uint8_t* frames, int n, int height, int wid
   if (rc) return rc;
   for (int off = 0; off < n; off += d->max_frames) {
     const int B = std::min(d->max_frames, n - off);
-    rc = forward_chunk(h, frames + (size_t)off * height * width * 3, B, height, width, g, s);
+    rc = forward_chunk(h, frames + (size_t)off * height * width * 3, B, height, width, g, d->tabs, s);
     if (rc) return rc;
     rc = postprocess_chunk(h, B, off, (float)g.det_scale, nullptr, "frame", det_thresh, max_faces, dets, counts, s);
     if (rc) return rc;
+  }
+  return FR_OK;
+}
+
+int detector_run_device(fr_handle* h, const uint8_t* frames, int n, int height, int width, float det_thresh,
+                        int max_faces, float* dets, int32_t* counts, hipStream_t s) {
+  Detector* d = h->det;
+  Geometry g;
+  const int* tabs = nullptr;
+  int rc = setup_geometry_cached(h, height, width, g, &tabs);
+  if (rc) return rc;
+  for (int off = 0; off < n; off += d->max_frames) {
+    const int B = std::min(d->max_frames, n - off);
+    rc = forward_chunk(h, frames + (size_t)off * height * width * 3, B, height, width, g, tabs, s);
+    if (rc) return rc;
+    // NMS writes the caller's rows and counts; a frame over the candidate limit then gets -1
+    rc = postprocess_device(h, B, (float)g.det_scale, nullptr, det_thresh, max_faces,
+                            dets + (size_t)off * max_faces * 15, counts + off, s);
+    if (rc) return rc;
+    const hipError_t e = launch_det_overflow(d->count, B, DET_MAX_CANDIDATES, counts + off, s);
+    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("detect counts: ") + hipGetErrorString(e));
   }
   return FR_OK;
 }
@@ -765,7 +846,7 @@ int detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int
   Geometry g;
   int rc = setup_geometry(h, height, width, g, s);
   if (rc) return rc;
-  rc = forward_chunk(h, frames, n, height, width, g, s);
+  rc = forward_chunk(h, frames, n, height, width, g, d->tabs, s);
   if (rc) return rc;
   return copy_heads_canvas(h, n, g, heads, canvas, s);
 }

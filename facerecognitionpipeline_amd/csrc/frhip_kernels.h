@@ -240,6 +240,32 @@ struct WarpFace {
 };
 hipError_t launch_warp_affine_images(const WarpFace* faces, int n, int S, uint8_t* out, hipStream_t s);
 
+// The similarity fit of fr_align_faces on the device (align_fit.hip), one lane per slot.
+// update_num_iters' logarithms for 5 points and confidence 0.99 (align_host.cpp fit_logs).
+struct FitLogs {
+  double log_num;     // log(max(1 - p, DBL_MIN))
+  double log_den[6];  // log(1 - q * q), q = 1 - (5 - g) / 5, per inlier count g
+  int den_zero;       // bit g: 1 - q * q < DBL_MIN (update_num_iters returns 0)
+};
+struct FitSlots {
+  const uint8_t* frames;   // device uint8 [n_frames][H][W][3], or NULL with faces == NULL
+  int n_frames, H, W;
+  const float* landmarks;  // device: slot j's 5 x (x, y) at landmarks + j * stride
+  int stride;
+  const int* counts;       // device [n_frames]: slots i < min(counts[f], max_faces) of frame f are live; NULL: all
+  int max_faces;           // slots per frame
+  float tmpl[10];          // reference_template(out_size)
+  FitLogs logs;
+  double* tforms;          // device [slots][6] forward maps (NaN for a slot that is not ok), or NULL
+  uint8_t* ok;             // device [slots]: 1 = live and fitted
+  WarpFace* faces;         // device [slots] descriptors for launch_warp_affine_images, or NULL
+};
+// Slot (f, i): fit_similarity(landmarks, tmpl, 5) bitwise as the host computes it; ok, the forward map
+// and the slot's WarpFace (frame f, H, W, invert_affine of the map).  A slot that is not live or whose
+// fit fails gets ok = 0, a NaN map and a descriptor of an empty (0 x 0) source: the warp writes
+// zeros and reads nothing.  n_frames * max_faces < 2^31.
+hipError_t launch_fit_similarity(const FitSlots& p, hipStream_t s);
+
 // Laplacian variance (numpy's summation order) of the gray image of n uint8 images [n][H][W][C]
 // (C = 3 / 4: RGB(A) -> gray; C = 1: gray) -> var[n] (double).  Images whose gray copy and
 // summation trees fit BLUR_LDS_MAX bytes of LDS take one block each; larger ones take three
@@ -432,5 +458,7 @@ hipError_t launch_row_expand(const float* x, int B, int Hs, int W, int C, int m,
 hipError_t launch_decode(const DetDecodeParams& p, int n, hipStream_t s);
 hipError_t launch_nms(const float* cand, const int* count, int n, int cap, float iou_thresh, int max_out, float* out,
                       int* out_count, hipStream_t s);
+// counts[f] = -1 for every frame f < n with raw[f] > cap (more candidates than decode kept).
+hipError_t launch_det_overflow(const int* raw, int n, int cap, int* counts, hipStream_t s);
 
 }  // namespace frhip

@@ -383,28 +383,42 @@ int fr_warp_affine(fr_handle* h, const uint8_t* frame, int height, int width, co
   return FR_OK;
 }
 
+namespace {
+// The blur launches of n checked images into var (device double [n]), under the handle's lock and
+// device: what fr_blur_scores and fr_blur_scores_device share.  Asynchronous.
+int blur_device(fr_handle* h, const uint8_t* crops, int n, int height, int width, int channels, double* var,
+                hipStream_t s) {
+  const size_t img = (size_t)height * width * channels;
+  const int per = 65535;  // images per launch (grid y of the multi-block form)
+  const size_t ws = blur_workspace_bytes(std::min(n, per), height, width);
+  if (ws)
+    if (int rc = ensure_buf(h, &h->blur_ws, &h->blur_ws_cap, ws)) return rc;
+  for (int off = 0; off < n; off += per) {
+    const int m = std::min(per, n - off);
+    const hipError_t e = launch_blur(crops + (size_t)off * img, m, height, width, channels, var + off, h->blur_ws, s);
+    if (e != hipSuccess) return launch_fail(h, "blur", e);
+  }
+  return FR_OK;
+}
+
+bool blur_args_ok(const uint8_t* crops, int n, int height, int width, int channels, const double* scores) {
+  return n >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31) &&
+         (channels == 1 || channels == 3 || channels == 4) && (n == 0 || (crops && scores));
+}
+}  // namespace
+
 int fr_blur_scores(fr_handle* h, const uint8_t* crops, int n, int height, int width, int channels, double* scores,
                    void* stream) {
   if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
   std::lock_guard<std::mutex> lk(h->mu);
-  if (n < 0 || height < 1 || width < 1 || (long long)height * width >= (1ll << 31) ||
-      (channels != 1 && channels != 3 && channels != 4) || (n > 0 && (!crops || !scores)))
+  if (!blur_args_ok(crops, n, height, width, channels, scores))
     return fail(h, FR_ERR_INVALID_ARGUMENT, "bad blur arguments (height, width >= 1; channels 1, 3 or 4)");
   if (n == 0) return FR_OK;
   DeviceGuard dg(h->device);
   int rc = ensure_buf(h, &h->blur_out, &h->blur_out_cap, (size_t)n * sizeof(double));
   if (rc) return rc;
-  const size_t img = (size_t)height * width * channels;
-  const int per = 65535;  // images per launch (grid y of the multi-block form)
-  const size_t ws = blur_workspace_bytes(std::min(n, per), height, width);
-  if (ws && (rc = ensure_buf(h, &h->blur_ws, &h->blur_ws_cap, ws))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  for (int off = 0; off < n; off += per) {
-    const int m = std::min(per, n - off);
-    hipError_t e = launch_blur(crops + (size_t)off * img, m, height, width, channels, (double*)h->blur_out + off,
-                               h->blur_ws, s);
-    if (e != hipSuccess) return launch_fail(h, "blur", e);
-  }
+  if ((rc = blur_device(h, crops, n, height, width, channels, (double*)h->blur_out, s))) return rc;
   FR_HIP(h, hipMemcpyAsync(scores, h->blur_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
   FR_HIP(h, hipStreamSynchronize(s));
   return check_dev_err(h);
@@ -481,6 +495,67 @@ int fr_align_images(fr_handle* h, const uint8_t* const* images, const int32_t* s
   if (e != hipSuccess) return launch_fail(h, "warp", e);
   FR_HIP(h, hipStreamSynchronize(s));
   return FR_OK;
+}
+
+int fr_detect_device(fr_handle* h, const uint8_t* frames, int n, int height, int width, float det_thresh,
+                     int max_faces, float* dets, int32_t* counts, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->detector) return fail(h, FR_ERR_STATE, "not a detector handle (fr_create(\"scrfd_10g\", \"scrfd\", ...))");
+  if (!h->finalized) return fail(h, FR_ERR_STATE, "model not finalised (fr_finalize)");
+  if (n < 0 || (n > 0 && (!frames || !counts || (max_faces > 0 && !dets))) || height < 2 || width < 2 ||
+      max_faces < 0)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad frames / sizes / output buffers");
+  if (n == 0) return FR_OK;
+  if (int rc = check_dev_err(h)) return rc;  // reported by earlier asynchronous work
+  DeviceGuard dg(h->device);
+  return detector_run_device(h, frames, n, height, width, det_thresh, max_faces, dets, counts, (hipStream_t)stream);
+}
+
+int fr_align_device(fr_handle* h, const uint8_t* frames, int n_frames, int height, int width, const float* landmarks,
+                    int stride, const int32_t* counts, int max_faces, int out_size, uint8_t* out, double* tforms,
+                    uint8_t* ok, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  const long long slots = (long long)n_frames * max_faces;
+  if (n_frames < 0 || max_faces < 0 || height <= 0 || width <= 0 || out_size <= 0 || out_size > 1024 || stride < 10 ||
+      slots >= (1ll << 31) || (slots > 0 && (!frames || !landmarks || !out || !ok)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad alignment arguments");
+  if (slots == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  // sized before the first launch; a call that fits the buffer allocates nothing
+  if (int rc = ensure_buf(h, &h->align_slots, &h->align_slots_cap, (size_t)slots * sizeof(WarpFace))) return rc;
+  FitSlots p{};
+  p.frames = frames;
+  p.n_frames = n_frames;
+  p.H = height;
+  p.W = width;
+  p.landmarks = landmarks;
+  p.stride = stride;
+  p.counts = counts;
+  p.max_faces = max_faces;
+  reference_template(out_size, p.tmpl);
+  fit_logs(&p.logs);
+  p.tforms = tforms;
+  p.ok = ok;
+  p.faces = static_cast<WarpFace*>(h->align_slots);
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = launch_fit_similarity(p, s);
+  if (e != hipSuccess) return launch_fail(h, "similarity fit", e);
+  e = launch_warp_affine_images(p.faces, (int)slots, out_size, out, s);
+  if (e != hipSuccess) return launch_fail(h, "warp", e);
+  return FR_OK;
+}
+
+int fr_blur_scores_device(fr_handle* h, const uint8_t* crops, int n, int height, int width, int channels,
+                          double* scores, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!blur_args_ok(crops, n, height, width, channels, scores))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad blur arguments (height, width >= 1; channels 1, 3 or 4)");
+  if (n == 0) return FR_OK;
+  DeviceGuard dg(h->device);
+  return blur_device(h, crops, n, height, width, channels, scores, (hipStream_t)stream);
 }
 
 int fr_set_precision(fr_handle* h, int mode) {

@@ -308,6 +308,43 @@ int frt_fit_similarity(const float* src, const float* dst, int n, double* M) {
   return fit_similarity(src, dst, n, M) ? FR_OK : fail(nullptr, FR_ERR_INVALID_ARGUMENT, "similarity fit failed");
 }
 
+int frt_fit_similarity_device(const float* landmarks, int n, int out_size, double* M, uint8_t* ok, float* ms) {
+  if (n < 1 || !landmarks || !M || !ok || out_size < 1)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_fit_similarity_device: bad arguments");
+  const size_t lm_bytes = (size_t)n * 10 * sizeof(float), m_bytes = (size_t)n * 6 * sizeof(double);
+  char* buf = nullptr;  // [maps | landmarks | ok]
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipMalloc((void**)&buf, m_bytes + lm_bytes + (size_t)n);
+  if (e == hipSuccess) e = hipMemcpy(buf + m_bytes, landmarks, lm_bytes, hipMemcpyHostToDevice);
+  FitSlots p{};
+  p.n_frames = 1;
+  p.landmarks = reinterpret_cast<const float*>(buf + m_bytes);
+  p.stride = 10;
+  p.max_faces = n;
+  reference_template(out_size, p.tmpl);
+  fit_logs(&p.logs);
+  p.tforms = reinterpret_cast<double*>(buf);
+  p.ok = reinterpret_cast<uint8_t*>(buf + m_bytes + lm_bytes);
+  if (e == hipSuccess) e = launch_fit_similarity(p, nullptr);
+  if (ms) {  // a second launch between two events: the first one also loaded the code object
+    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], nullptr);
+    if (e == hipSuccess) e = launch_fit_similarity(p, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+    if (e == hipSuccess) e = hipEventElapsedTime(ms, ev[0], ev[1]);
+  }
+  if (e == hipSuccess) e = hipMemcpy(M, p.tforms, m_bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ok, p.ok, (size_t)n, hipMemcpyDeviceToHost);
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  (void)hipFree(buf);
+  if (e != hipSuccess)
+    return fail(nullptr, FR_ERR_HIP, std::string("frt_fit_similarity_device: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
 int frt_detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int width, float* heads,
                          uint8_t* canvas, void* stream) {
   if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");

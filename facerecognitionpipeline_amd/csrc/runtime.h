@@ -222,6 +222,10 @@ struct fr_handle {
   size_t blur_out_cap = 0;
   void* blur_ws = nullptr;  // multi-block blur: per (image, chunk) int64 L sums + double values
   size_t blur_ws_cap = 0;
+  // fr_align_device: [slots] WarpFace written by the fit kernel (a buffer of its own: the call is
+  // asynchronous, and a captured graph keeps replaying into it)
+  void* align_slots = nullptr;
+  size_t align_slots_cap = 0;
 
   int cus = 0;  // CUs of the device (ensure_stream_k)
   bool stream_k = true;
@@ -334,6 +338,7 @@ struct fr_handle {
     (void)hipFree(align_m);
     (void)hipFree(blur_out);
     (void)hipFree(blur_ws);
+    (void)hipFree(align_slots);
     if (dev_err) (void)hipHostFree(dev_err);
   }
 };
@@ -486,6 +491,8 @@ int gallery_reserve(fr_handle* h, int rows, hipStream_t s);
 // estimateAffinePartial2D(src, dst)[0]: returns false (M NaN) where cv2 returns None
 bool fit_similarity(const float* src, const float* dst, int n, double M[6]);
 void invert_affine(const double Mf[6], double Mi[6]);
+// what the device fit takes in place of update_num_iters' logarithms (frhip_kernels.h FitLogs)
+void fit_logs(frhip::FitLogs* lg);
 void augment_tables(int H, int W, frhip::AugTables* t);
 void reference_template(int S, float t[10]);
 
@@ -498,6 +505,11 @@ std::map<std::string, size_t> detector_schema();
 int detector_finalize(fr_handle* h);
 int detector_run(fr_handle* h, const uint8_t* frames, int n, int height, int width, float det_thresh, int max_faces,
                  float* dets, int32_t* counts, hipStream_t s);
+// fr_detect_device: detector_run's launches with dets [n][max_faces][15] and counts [n] on the
+// device (NMS writes them in place; counts[f] = -1 for a frame over the candidate limit) and the
+// resize tables cached per frame size.  Asynchronous on s once the size has been seen.
+int detector_run_device(fr_handle* h, const uint8_t* frames, int n, int height, int width, float det_thresh,
+                        int max_faces, float* dets, int32_t* counts, hipStream_t s);
 int detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int width, float* heads,
                      uint8_t* canvas, hipStream_t s);
 // The same for n images of their own sizes (host arrays: images[n] device pointers, sizes[n][2] =

@@ -11,6 +11,9 @@ frame uploaded once:
 
 Detections come from any detector with the reference ``FaceDetector.detect``
 contract (``face_recognition.py:31-48``), the GPU SCRFD ``FaceDetector`` included.
+``recognize_frames`` starts from the frames instead and keeps the whole chain on the
+device: detect, align and blur write device buffers (fr_detect_device, fr_align_device,
+fr_blur_scores_device), and a batch of frames crosses to the host once, for the gate.
 ``MatchBatcher`` batches concurrent single-face requests the same way.
 """
 from __future__ import annotations
@@ -25,14 +28,16 @@ import numpy as np
 import torch
 
 from .face_embedder import FaceEmbedder, as_uint8_crop
-from .face_recognition import FaceAligner, FaceQualityFilter
+from .face_recognition import FaceAligner, FaceDetector, FaceQualityFilter
 from .gallery_manager import GalleryManager, _slice_len
 
 
 class RecognitionPipeline:
     def __init__(self, embedder: FaceEmbedder, gallery: GalleryManager,
-                 quality_filter_config: Optional[Dict] = None, similarity_threshold: float = 0.4):
+                 quality_filter_config: Optional[Dict] = None, similarity_threshold: float = 0.4,
+                 detector: Optional[FaceDetector] = None):
         self.embedder = embedder
+        self.detector = detector  # recognize_frames builds one on first use when None
         self.gallery = gallery
         self.gallery.attach_handle(embedder.model)
         dev = embedder.device
@@ -71,6 +76,69 @@ class RecognitionPipeline:
             m = res[row]
             out[i]["matches"] = m
             out[i]["recognized"] = bool(m) and m[0][2] >= self.similarity_threshold
+        return out
+
+    def recognize_frames(self, frames, top_k: int = 3, max_faces: Optional[int] = None) -> List[List[Dict]]:
+        """``recognize`` for a batch of frames, detection included: uint8 [n,H,W,3] RGB frames of one
+        size (host array or device tensor) -> one list per frame of the dicts ``recognize(frame,
+        detections)`` returns for the GPU detector's detections of that frame.
+
+        detect_device -> align_device -> blur_scores_device run back to back on the device with
+        ``max_faces`` slots per frame (default: the detector's ``max_faces``; crops of every slot are
+        held, n * max_faces * 37.6 kB); then ONE copy brings dets, counts, ok and the blur scores to the
+        host for the quality gate, and the valid crops are gathered on the device for one
+        ``embed_match``.  A frame over the detector's 4096-candidate limit raises the
+        ``NotImplementedError`` that ``FaceDetector.detect`` raises for it; a detection whose
+        similarity fit fails (where ``recognize`` raises) comes back ``is_valid: False``."""
+        dev = self.embedder.device
+        if self.detector is None:
+            self.detector = FaceDetector(device=dev)
+        det = self.detector
+        if det.device != dev:
+            raise ValueError(f"the detector is on {det.device}, the embedder on {dev}")
+        t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8))
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError("expected uint8 [n,H,W,3] RGB frames")
+        n = t.shape[0]
+        if n == 0:
+            return []
+        t = t.to(dev).contiguous()
+        F = det.max_faces if max_faces is None else int(max_faces)
+        S = self.aligner.output_size
+        dets, counts = det.model.detect_device(t, det.det_thresh, F)
+        crops, _, ok = self.aligner._ops.handle.align_device(t, dets, counts, S)
+        crops = crops.view(n * F, S, S, 3)
+        blur = self.quality._ops.handle.blur_scores_device(crops) if self.quality.check_blur else dets.new_empty(
+            0, dtype=torch.float64)
+        parts = [blur.view(torch.uint8), dets.view(-1).view(torch.uint8), counts.view(torch.uint8), ok.view(-1)]
+        host = torch.cat(parts).cpu().numpy()  # the chain's one copy and its one synchronisation
+        cut = np.cumsum([p.numel() for p in parts])
+        h_blur = host[:cut[0]].view(np.float64).reshape(n, F) if self.quality.check_blur else None
+        h_dets = host[cut[0]:cut[1]].view(np.float32).reshape(n, F, 15)
+        h_counts = host[cut[1]:cut[2]].view(np.int32)
+        h_ok = host[cut[2]:].reshape(n, F)
+        for f in range(n):
+            if h_counts[f] < 0:
+                raise NotImplementedError(f"frame {f} has more than 4096 anchors above det_thresh (limit 4096)")
+        out: List[List[Dict]] = []
+        valid = []  # (frame, face) of the crops to embed, in output order
+        for f in range(n):
+            rows = []
+            for i, d in enumerate(det._faces(h_dets[f], min(int(h_counts[f]), F))):
+                good, q = self.quality.is_valid(d, None, None if h_blur is None else float(h_blur[f, i]))
+                good = good and bool(h_ok[f, i])
+                rows.append({"bbox": d.get("bbox"), "det_score": d["det_score"], "quality_metrics": q,
+                             "is_valid": good, "matches": [], "recognized": False})
+                if good:
+                    valid.append((f, i))
+            out.append(rows)
+        if not valid:
+            return out
+        sel = crops[torch.tensor([f * F + i for f, i in valid], device=dev)].contiguous()
+        res = self.gallery.match_resolved(len(valid), top_k, lambda h, k, idx, score: h.embed_match(sel, k, idx, score))
+        for m, (f, i) in zip(res, valid):
+            out[f][i]["matches"] = m
+            out[f][i]["recognized"] = bool(m) and m[0][2] >= self.similarity_threshold
         return out
 
 

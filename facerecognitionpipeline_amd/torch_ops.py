@@ -23,6 +23,9 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
                                                                3, 10, 10.0, 0.6)                # [N] x 3, [T,4] i32
     scores = torch.ops.frhip.identity_scores(q, gallery_rows, id_offsets, "mean", 3)   # [N, n_ids] f32
     rec_i, rec_f, counts = torch.ops.frhip.eval_probes(scores, true_id, thresholds)    # [N,4] x 2, [T,4] i64
+    dets, counts = torch.ops.frhip.detect(frames_u8_nhwc, det_hid, 0.5, 16)            # [N,16,15] f32, [N] i32
+    crops, tforms, ok = torch.ops.frhip.align_detections(frames, dets, counts, 112)    # [N,16,112,112,3] u8, f64, u8
+    blur = torch.ops.frhip.blur_scores(crops.flatten(0, 1))                            # [N*16] f64
 
 Each op has a fake (meta) implementation, so the ops trace under
 ``torch.fx`` / ``torch.export`` with the right output shapes.
@@ -70,7 +73,7 @@ _utility: Dict[torch.device, "_lib.Handle"] = {}
 
 def utility_handle(device) -> "_lib.Handle":
     """A model-less handle on ``device`` for the entry points that need no weights
-    (``augment_faces``, ``track_consensus``, ``photo_rollcall``, ``capture_tracks``, ``live_tracks``, ``server_tracks``, ``identity_scores``, ``eval_probes``): one per device, created on first use."""
+    (``augment_faces``, ``track_consensus``, ``photo_rollcall``, ``capture_tracks``, ``live_tracks``, ``server_tracks``, ``identity_scores``, ``eval_probes``, ``align_detections``, ``blur_scores``): one per device, created on first use."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
@@ -302,3 +305,45 @@ def _(scores, true_id, thresholds):
     n = scores.shape[0]
     return (scores.new_empty((n, 4), dtype=torch.int32), scores.new_empty((n, 4), dtype=torch.float32),
             scores.new_empty((len(thresholds), 4), dtype=torch.int64))
+
+
+# The frames -> (detections, crops, blur) chain on device tensors: no host copy and no
+# synchronisation in any of the three (fr_detect_device / fr_align_device / fr_blur_scores_device).
+@torch.library.custom_op("frhip::detect", mutates_args=())
+def detect(frames: torch.Tensor, handle: int, det_thresh: float, max_faces: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _get(handle).detect_device(frames, det_thresh, max_faces)
+
+
+@detect.register_fake
+def _(frames, handle, det_thresh, max_faces):
+    n = frames.shape[0]
+    return frames.new_empty((n, max_faces, 15), dtype=torch.float32), frames.new_empty((n,), dtype=torch.int32)
+
+
+@torch.library.custom_op("frhip::align_detections", mutates_args=())
+def align_detections(frames: torch.Tensor, dets: torch.Tensor, counts: torch.Tensor,
+                     out_size: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    if frames.device.type != "cuda":
+        raise ValueError(f"frames are on {frames.device}: align_detections runs on a HIP device (no CPU fallback)")
+    if dets.dim() != 3 or dets.shape[2] != 15:
+        raise ValueError("expected detection rows float32 [N,F,15] (frhip::detect's dets)")
+    return utility_handle(frames.device).align_device(frames, dets, counts, out_size)
+
+
+@align_detections.register_fake
+def _(frames, dets, counts, out_size):
+    n, f = dets.shape[0], dets.shape[1]
+    return (frames.new_empty((n, f, out_size, out_size, 3), dtype=torch.uint8),
+            frames.new_empty((n, f, 2, 3), dtype=torch.float64), frames.new_empty((n, f), dtype=torch.uint8))
+
+
+@torch.library.custom_op("frhip::blur_scores", mutates_args=())
+def blur_scores(crops: torch.Tensor) -> torch.Tensor:
+    if crops.device.type != "cuda":
+        raise ValueError(f"crops are on {crops.device}: blur_scores runs on a HIP device (no CPU fallback)")
+    return utility_handle(crops.device).blur_scores_device(crops)
+
+
+@blur_scores.register_fake
+def _(crops):
+    return crops.new_empty((crops.shape[0],), dtype=torch.float64)

@@ -569,6 +569,50 @@ int fr_resize_images(fr_handle* h, const uint8_t* const* images /* host [n] devi
 int fr_embed_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n,
                     float* out /* device [n][512] */, int normalize, void* stream);
 
+/* ---- The frames -> (detections, crops, blur) chain with device outputs.  The three calls below
+ * are fr_detect, fr_align_faces and fr_blur_scores with every output in device memory: they are
+ * asynchronous on `stream`, synchronise nothing and read no host memory after they return, so the
+ * chain can run behind other work, be captured in a hipGraph, and a batch of frames needs one
+ * device -> host copy (of dets, counts, ok and the blur scores) before the host quality gate.
+ * While a captured graph of them is in use, the handle's workspace it was captured with must stay:
+ * make no fr_align_device call with more slots and no multi-block fr_blur_scores* call with more
+ * images than the captured ones. */
+
+/* fr_detect with dets (device float [n][max_faces][15]) and counts (device int32 [n]) on the
+ * device: the same chunks of max_frames, the same row reduction, the same kernels, NMS writing
+ * the caller's rows, so counts[f] and rows i < min(counts[f], max_faces) are bitwise fr_detect's
+ * (the other rows are not written).  A frame with more than 4096 anchors above det_thresh, where
+ * fr_detect returns FR_ERR_UNSUPPORTED, gets counts[f] = -1 (its rows are unspecified); the other
+ * frames of the call are unaffected.  The letterbox resize tables are kept on the device per frame
+ * size (the last 16 sizes): the first call on a size allocates and uploads its tables with one
+ * synchronous copy (not capturable: warm a size up once), a later call copies nothing. */
+int fr_detect_device(fr_handle* h, const uint8_t* frames /* device [n][height][width][3] */, int n, int height,
+                     int width, float det_thresh, int max_faces, float* dets, int32_t* counts, void* stream);
+
+/* FaceAligner.align for n_frames frames of one size with max_faces slots each, landmarks read from
+ * device memory: slot j = f * max_faces + i reads its 5 x (x, y) floats at landmarks + j * stride
+ * (stride >= 10; fr_detect_device's dets + 5 with stride 15 reads detection rows in place), and is
+ * live when i < min(counts[f], max_faces) (counts: device int32 [n_frames], a negative count makes
+ * none live; NULL: every slot is live).  One kernel fits every live slot (one lane each: the host
+ * fit of fr_align_faces restated for the device, bitwise its doubles), one launch warps all slots.
+ *   ok (device uint8 [slots]): 1 for a live slot whose fit succeeded.  Then out[j] (device uint8
+ *     [slots][out_size][out_size][3]) and tforms[j] (device double [slots][2][3], or NULL) are
+ *     bitwise fr_align_faces' for that frame and that face alone.
+ *   Every other slot (not live, or a fit cv2 returns None for, which fr_align_faces refuses) has
+ *     ok = 0, an all-zero crop and a NaN tform; no source pixel is read for it.
+ * Any handle will do, finalised or not.  Allocates only when the call has more slots than any
+ * before it.  FR_ERR_INVALID_ARGUMENT: NULL buffers, a side < 1, out_size outside [1, 1024],
+ * stride < 10, n_frames * max_faces >= 2^31.  Zero slots is a no-op. */
+int fr_align_device(fr_handle* h, const uint8_t* frames /* device [n_frames][height][width][3] */, int n_frames,
+                    int height, int width, const float* landmarks /* device */, int stride,
+                    const int32_t* counts /* device [n_frames] or NULL */, int max_faces, int out_size,
+                    uint8_t* out, double* tforms, uint8_t* ok, void* stream);
+
+/* fr_blur_scores with scores in device memory (double [n]): the same launches, no copy and no
+ * synchronisation; the values are bitwise fr_blur_scores'. */
+int fr_blur_scores_device(fr_handle* h, const uint8_t* crops, int n, int height, int width, int channels,
+                          double* scores /* device [n] */, void* stream);
+
 /* Conv arithmetic of this handle.  FR_PRECISION_F32 (default): exact f32 products and f32
  * accumulation on fp32 MFMA -- the parity path.  FR_PRECISION_BF16X3 (opt-in fast mode):
  * each f32 operand split into bf16 hi + lo, x.y ~= hi.hi + hi.lo + lo.hi on bf16 MFMA with f32

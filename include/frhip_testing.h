@@ -115,6 +115,12 @@ int frt_stem(const uint8_t* img, int B, const float* lut, const float* w27x64, c
 /* The host similarity fit of fr_align_faces: src/dst float [n][2] -> M double [2][3]. */
 int frt_fit_similarity(const float* src, const float* dst, int n, double* M);
 
+/* The device similarity fit of fr_align_device alone: n landmark sets (host float [n][5][2]) against
+ * the reference template of out_size -> M (host double [n][2][3], NaN where ok is 0) and ok (host
+ * uint8 [n]).  Stages through temporary device buffers on the current device and synchronises.
+ * With ms != NULL also the kernel's time between two HIP events of one more launch (milliseconds). */
+int frt_fit_similarity_device(const float* landmarks, int n, int out_size, double* M, uint8_t* ok, float* ms);
+
 /* The detector stem's MaxPool2d(3, 2, 1) alone: x [B][H][W][C] -> y [B][(H+1)/2][(W+1)/2][C], NHWC
  * f32, C % 4 == 0, 16-byte aligned.  Asynchronous on stream. */
 int frt_maxpool3(const float* x, int B, int H, int W, int C, float* y, void* stream);
