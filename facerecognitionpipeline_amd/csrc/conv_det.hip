@@ -1,6 +1,8 @@
-// Detector instances of the implicit-GEMM conv kernel (conv_mfma_impl.h): no pre-BN,
-// conv + BN + ReLU (zero PReLU slopes) and BasicBlock conv2 + BN + residual + ReLU,
-// on the tiles the SCRFD layer shapes use (detector.cpp).  f32 only.
+// Detector instances of the implicit-GEMM conv kernel (conv_mfma_impl.h): no pre-BN, two
+// epilogues per tile: conv + BN + ReLU (EPI_AFFINE_PRELU with zero PReLU slopes) and BasicBlock
+// conv2 + BN + residual + ReLU (EPI_AFFINE_RES_PRELU), on the three tiles the SCRFD layer shapes
+// use (conv_dispatch.cpp); any other tile or epilogue is refused.  The detector's EPI_AFFINE and
+// EPI_AFFINE_RES convs run on the embedding set's instances (conv_f32_w4 / conv_f32_w8).  f32 only.
 #include "conv_mfma_impl.h"
 
 namespace frhip {

@@ -560,7 +560,9 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_mfma_kernel(ConvParams p
 }
 
 // SET selects the (PRE, EPI) instances a translation unit compiles: 0 = the embedding
-// network's, 1 = the detector's (no pre-BN; ReLU via zero PReLU slopes).
+// network's, 1 = the detector's own two (no pre-BN; ReLU via zero PReLU slopes): EPI_AFFINE_PRELU
+// and EPI_AFFINE_RES_PRELU, the only epilogues launch_conv routes to launch_conv_det.  The
+// detector's EPI_AFFINE / EPI_AFFINE_RES convs run on set 0's instances.
 template <int BM, int BN, int WM, int WN, bool SPLIT, int SET = 0>
 static hipError_t launch_tile(const ConvParams& p0, bool pre, Epi epi, int nsplit, hipStream_t s) {
   constexpr int NTHREADS = 64 * WM * WN;
@@ -585,9 +587,7 @@ static hipError_t launch_tile(const ConvParams& p0, bool pre, Epi epi, int nspli
         FR_OCC_CASE(true, EPI_RAW)
         FR_OCC_CASE(false, EPI_RAW)
       } else {
-        FR_OCC_CASE(false, EPI_AFFINE)
         FR_OCC_CASE(false, EPI_AFFINE_PRELU)
-        FR_OCC_CASE(false, EPI_AFFINE_RES)
         FR_OCC_CASE(false, EPI_AFFINE_RES_PRELU)
       }
 #undef FR_OCC_CASE
@@ -627,9 +627,7 @@ static hipError_t launch_tile(const ConvParams& p0, bool pre, Epi epi, int nspli
     FR_CONV_CASE(true, EPI_RAW)
     FR_CONV_CASE(false, EPI_RAW)
   } else {
-    FR_CONV_CASE(false, EPI_AFFINE)
     FR_CONV_CASE(false, EPI_AFFINE_PRELU)
-    FR_CONV_CASE(false, EPI_AFFINE_RES)
     FR_CONV_CASE(false, EPI_AFFINE_RES_PRELU)
   }
 #undef FR_CONV_CASE

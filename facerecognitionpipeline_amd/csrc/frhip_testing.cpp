@@ -25,21 +25,36 @@ static int set_handle_knob(fr_handle* h, Set set) {
 
 extern "C" {
 
-int frt_conv2d(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout, int kh, int kw,
-               int stride, int pad, const float* pre_scale, const float* pre_shift, const float* post_scale,
-               const float* post_shift, const float* prelu, const float* res, int res_h, int res_w, int epi,
-               int nsplit, int tile, int stream_k, int precision, void* stream) {
+// frt_conv2d / frt_conv2d_fused: one launch_conv, a ConvParams built as run_conv builds it
+// (conv_shape of a ConvW with cin2 > 0 sets steps1 / steps_total of the fused shortcut).
+// Only what would dereference a null pointer is refused here; every other rule (channel multiples,
+// which epilogues take pre-BN or a fused shortcut, the tiles of the detector's instances) is left
+// to launch_conv, so tests pin the launcher's refusals, not this wrapper's.
+static int conv2d_entry(const char* who, const float* x, const float* x2, const float* w, float* y, int B, int H, int W,
+                        int cin, int cin2, int cout, int kh, int kw, int stride, int pad, const float* pre_scale,
+                        const float* pre_shift, const float* post_scale, const float* post_shift, const float* prelu,
+                        const float* res, int res_h, int res_w, int epi, int nsplit, int tile, int stream_k,
+                        int precision, void* stream) {
   static int t_cus = 0, t_cap = 0;
   static float* t_ws = nullptr;
   static long long t_wsf = 0;
   static int* t_cnt = nullptr;
-  if (epi < 0 || epi > 4 || nsplit < 1 || (nsplit > 1 && epi != EPI_RAW) || (tile < 0 || tile >= TILE_COUNT) ||
-      stride < 1 || kh < 1 || kw < 1 || B < 1)
-    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d: bad arguments");
+  const bool res_epi = epi == EPI_AFFINE_RES || epi == EPI_AFFINE_RES_SUB || epi == EPI_AFFINE_RES_PRELU;
+  const bool prelu_epi = epi == EPI_AFFINE_PRELU || epi == EPI_AFFINE_RES_PRELU;
+  if (epi < 0 || epi > EPI_AFFINE_RES_PRELU || nsplit < 1 || (nsplit > 1 && epi != EPI_RAW) ||
+      (tile < 0 || tile >= TILE_COUNT) || stride < 1 || kh < 1 || kw < 1 || B < 1 || H < 1 || W < 1 || cin < 1 ||
+      cout < 1 || cin2 < 0 || pad < 0 || H + 2 * pad < kh || W + 2 * pad < kw)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, std::string(who) + ": bad arguments");
+  if (!x || !w || !y || (cin2 > 0 && !x2) || ((pre_scale != nullptr) != (pre_shift != nullptr)) ||
+      (epi != EPI_RAW && (!post_scale || !post_shift)) || (prelu_epi && !prelu) || (res_epi && !res) ||
+      (epi == EPI_AFFINE_RES_SUB && (res_h < 1 || res_w < 1)) || (epi == EPI_AFFINE_RES_PRELU && pre_scale))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, std::string(who) + ": a pointer this epilogue reads is missing");
   ConvW cw;
   cw.geometry(cin, cout, kh, kw, stride, pad);
+  cw.cin2 = cin2;
   ConvParams p = conv_shape(cw, B, H, W, nsplit);
   p.x = x;
+  p.x2 = cin2 > 0 ? x2 : nullptr;
   p.w = w;
   p.y = y;
   p.pre_scale = pre_scale;
@@ -55,7 +70,7 @@ int frt_conv2d(const float* x, const float* w, float* y, int B, int H, int W, in
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (ensure_stream_k(dev, &t_cus, &t_ws, &t_wsf, &t_cnt, &t_cap) != FR_OK)
-      return fail(nullptr, FR_ERR_HIP, "frt_conv2d: stream-K workspace allocation failed");
+      return fail(nullptr, FR_ERR_HIP, std::string(who) + ": stream-K workspace allocation failed");
     p.sk_cus = t_cus;
     p.sk_ws = t_ws;
     p.sk_ws_floats = t_wsf;
@@ -64,7 +79,50 @@ int frt_conv2d(const float* x, const float* w, float* y, int B, int H, int W, in
   }
   hipError_t e = launch_conv(p, (ConvTile)tile, pre_scale != nullptr, (Epi)epi, nsplit, (hipStream_t)stream,
                              precision == 1 ? PREC_BF16X3 : PREC_F32);
-  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_conv2d(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout, int kh, int kw,
+               int stride, int pad, const float* pre_scale, const float* pre_shift, const float* post_scale,
+               const float* post_shift, const float* prelu, const float* res, int res_h, int res_w, int epi,
+               int nsplit, int tile, int stream_k, int precision, void* stream) {
+  return conv2d_entry("frt_conv2d", x, nullptr, w, y, B, H, W, cin, 0, cout, kh, kw, stride, pad, pre_scale, pre_shift,
+                      post_scale, post_shift, prelu, res, res_h, res_w, epi, nsplit, tile, stream_k, precision, stream);
+}
+
+int frt_conv2d_fused(const float* x, const float* x2, const float* w, float* y, int B, int H, int W, int cin, int cin2,
+                     int cout, int kh, int kw, int stride, int pad, const float* pre_scale, const float* pre_shift,
+                     const float* post_scale, const float* post_shift, const float* prelu, const float* res, int res_h,
+                     int res_w, int epi, int nsplit, int tile, int stream_k, int precision, void* stream) {
+  return conv2d_entry("frt_conv2d_fused", x, x2, w, y, B, H, W, cin, cin2, cout, kh, kw, stride, pad, pre_scale,
+                      pre_shift, post_scale, post_shift, prelu, res, res_h, res_w, epi, nsplit, tile, stream_k,
+                      precision, stream);
+}
+
+int frt_conv_split_fixup(const float* part, int S, long long stride, int B, int Ho, int Wo, int cout,
+                         const float* post_scale, const float* post_shift, const float* res, int res_h, int res_w,
+                         int epi, float* y, void* stream) {
+  const bool sub = epi == EPI_AFFINE_RES_SUB;
+  if (!part || !y || !post_scale || !post_shift || B < 1 || Ho < 1 || Wo < 1 || cout < 1 ||
+      (long long)B * Ho * Wo * cout >= (1ll << 31) || stride < (long long)B * Ho * Wo * cout ||
+      ((epi == EPI_AFFINE_RES || sub) && !res) ||
+      (sub && (res_h < 2 * (Ho - 1) + 1 || res_w < 2 * (Wo - 1) + 1)))  // the pixel (2 oy, 2 ox) must exist
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv_split_fixup: bad arguments");
+  ConvParams p{};  // exactly the fields conv_split_fixup_kernel reads
+  p.y = y;
+  p.post_scale = post_scale;
+  p.post_shift = post_shift;
+  p.res = res;
+  p.M = B * Ho * Wo;
+  p.Cout = cout;
+  p.Ho = Ho;
+  p.Wo = Wo;
+  p.res_H = res_h;
+  p.res_W = res_w;
+  const hipError_t e = launch_conv_split_fixup(p, (Epi)epi, part, S, stride, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv_split_fixup: refused");
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv_split_fixup: ") + hipGetErrorString(e));
   return FR_OK;
 }
 

@@ -2,8 +2,8 @@
  * frhip_testing.h — kernel-level entry points of libfrhip for parity tests.
  *
  * Not part of the drop-in surface (include/frhip.h): these expose single
- * kernels so tests can compare each against a PyTorch-CPU fp32 op of the same
- * shape (one Conv2d of net.BasicBlockIR, the stem, the matcher's top-k).
+ * kernels so tests can compare each against a PyTorch-CPU op of the same shape
+ * (one Conv2d of net.BasicBlockIR, the stem, the matcher's top-k).
  * All pointers are device pointers; every call is asynchronous on `stream`.
  */
 #ifndef FRHIP_TESTING_H_
@@ -17,16 +17,39 @@ extern "C" {
 
 /* y = epi(conv(pre(x))) in NHWC f32, w [cout][kh][kw][cin].
  * epi: 0 affine, 1 affine+PReLU, 2 affine+residual(res same shape as y),
- *      3 affine+residual(res[b][2oy][2ox], res spatial res_h x res_w), 4 raw.
+ *      3 affine+residual(res[b][2oy][2ox], res spatial res_h x res_w), 4 raw,
+ *      5 PReLU(affine+residual(res same shape as y)), no pre-affine (the detector's BasicBlock conv2).
  * pre_scale/pre_shift may be NULL (no pre-affine).  nsplit > 1 only with epi 4:
  * y then holds nsplit partial slabs of B*Ho*Wo*cout floats.
- * tile: 0 = 256x64, 1 = 128x128, 2 = 128x64, 3 = 64x128, 4 = 256x128, 5 = 128x256.
+ * epi 1 without pre-affine and epi 5 run the detector's instances (conv_det.hip: tiles 6, 7, 8
+ * only, f32 whatever `precision`); any other tile is refused (FR_ERR_HIP, y untouched).
+ * A pointer the epilogue reads that is NULL (post_* unless epi 4, prelu for epi 1 / 5, res for
+ * epi 2 / 3 / 5, one of pre_scale / pre_shift alone) or a pre-affine with epi 5 is
+ * FR_ERR_INVALID_ARGUMENT before any launch.
+ * tile: 0 = 256x64, 1 = 128x128, 2 = 128x64, 3 = 64x128, 4 = 256x128, 5 = 128x256, and with 8
+ * waves 6 = 128x128, 7 = 256x128, 8 = 128x64, 9 = 64x256, 10 = 256x64.
  * stream_k: 1 = persistent stream-K schedule (nsplit must be 1), 0 = one block per tile.
  * precision: 0 = f32 MFMA, 1 = bf16x3 split (tiles 1, 3, 4, 6, 7, 8 only). */
 int frt_conv2d(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout, int kh, int kw,
                int stride, int pad, const float* pre_scale, const float* pre_shift, const float* post_scale,
                const float* post_shift, const float* prelu, const float* res, int res_h, int res_w, int epi,
                int nsplit, int tile, int stream_k, int precision, void* stream);
+/* frt_conv2d with the kernel's fused 1x1 shortcut (ConvParams::x2 / Cin2 / steps1, set as the
+ * runtime sets them for a conv with cin2 > 0): y = epi(conv(x) + conv1x1 stride `stride` (x2)),
+ * x2 [B][H][W][cin2], w [cout][kh*kw*cin + cin2] (the shortcut's columns last).  launch_conv
+ * refuses cin2 % 32 != 0, a pre-affine and epi 1 / 5 with cin2 > 0 (FR_ERR_HIP, y untouched).
+ * cin2 = 0 is frt_conv2d. */
+int frt_conv2d_fused(const float* x, const float* x2, const float* w, float* y, int B, int H, int W, int cin, int cin2,
+                     int cout, int kh, int kw, int stride, int pad, const float* pre_scale, const float* pre_shift,
+                     const float* post_scale, const float* post_shift, const float* prelu, const float* res, int res_h,
+                     int res_w, int epi, int nsplit, int tile, int stream_k, int precision, void* stream);
+/* The split-K finish of a serving-sized stride-2 conv2 alone (conv_split_fixup_kernel):
+ * y [B][Ho][Wo][cout] = epi(sum over s < S of part[s * stride + i], in split order), epi 0, 2 (res
+ * shaped like y) or 3 (res [B][res_h][res_w][cout] read at (2 oy, 2 ox)); S in [1, 32], stride >=
+ * B*Ho*Wo*cout floats.  Arguments the launcher refuses -> FR_ERR_INVALID_ARGUMENT.  Asynchronous. */
+int frt_conv_split_fixup(const float* part, int S, long long stride, int B, int Ho, int Wo, int cout,
+                         const float* post_scale, const float* post_shift, const float* res, int res_h, int res_w,
+                         int epi, float* y, void* stream);
 
 /* Winograd F(2x2,3x3) stride-1 pad-1 conv (the FR_CONV_WINOGRAD path): same tensors as
  * frt_conv2d with kh = kw = 3; w is the untransformed [cout][3][3][cin] filter (transformed

@@ -14,6 +14,10 @@ def lib():
     if not getattr(L, "_frt_ready", False):
         L.frt_conv2d.restype = _I
         L.frt_conv2d.argtypes = [_P, _P, _P] + [_I] * 9 + [_P] * 6 + [_I] * 7 + [_P]
+        L.frt_conv2d_fused.restype = _I
+        L.frt_conv2d_fused.argtypes = [_P, _P, _P, _P] + [_I] * 10 + [_P] * 6 + [_I] * 7 + [_P]
+        L.frt_conv_split_fixup.restype = _I
+        L.frt_conv_split_fixup.argtypes = [_P, _I, ctypes.c_longlong] + [_I] * 4 + [_P] * 3 + [_I] * 3 + [_P, _P]
         L.frt_conv2d_winograd.restype = _I
         L.frt_conv2d_winograd.argtypes = [_P, _P, _P] + [_I] * 5 + [_P] * 6 + [_I, _P]
         L.frt_conv2d_winograd4.restype = _I
@@ -76,12 +80,21 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-def conv2d(x, w, B, H, W, cin, cout, kh, kw, stride, pad, pre=None, post=None, prelu=None, res=None,
-           res_hw=(0, 0), epi=0, nsplit=1, tile=1, stream_k=0, precision=0):
-    """x: NHWC cuda f32, w: [cout][kh][kw][cin] cuda f32.  Returns y (NHWC) or partial slabs."""
+def _conv_out(x, B, H, W, cout, kh, kw, stride, pad, nsplit, out):
+    """The NaN-filled output of a conv wrapper, or the caller's `out` of that shape (a test of a
+    refusal passes its own, to see after the raise that nothing was written)."""
     Ho = (H + 2 * pad - kh) // stride + 1
     Wo = (W + 2 * pad - kw) // stride + 1
-    y = torch.full((nsplit, B, Ho, Wo, cout), float("nan"), device=x.device)
+    if out is None:
+        return torch.full((nsplit, B, Ho, Wo, cout), float("nan"), device=x.device)
+    assert out.shape == (nsplit, B, Ho, Wo, cout) and out.dtype == torch.float32 and out.is_contiguous()
+    return out
+
+
+def conv2d(x, w, B, H, W, cin, cout, kh, kw, stride, pad, pre=None, post=None, prelu=None, res=None,
+           res_hw=(0, 0), epi=0, nsplit=1, tile=1, stream_k=0, precision=0, out=None):
+    """x: NHWC cuda f32, w: [cout][kh][kw][cin] cuda f32.  Returns y (NHWC) or partial slabs."""
+    y = _conv_out(x, B, H, W, cout, kh, kw, stride, pad, nsplit, out)
     ps, ph = (pre if pre is not None else (None, None))
     qs, qh = (post if post is not None else (None, None))
     rc = lib().frt_conv2d(_p(x), _p(w), _p(y), B, H, W, cin, cout, kh, kw, stride, pad, _p(ps), _p(ph), _p(qs),
@@ -89,6 +102,30 @@ def conv2d(x, w, B, H, W, cin, cout, kh, kw, stride, pad, pre=None, post=None, p
                           torch.cuda.current_stream().cuda_stream)
     _lib.check(rc)
     return y if nsplit > 1 else y[0]
+
+
+def conv2d_fused(x, x2, w, B, H, W, cin, cin2, cout, kh, kw, stride, pad, pre=None, post=None, prelu=None, res=None,
+                 res_hw=(0, 0), epi=0, nsplit=1, tile=1, stream_k=0, precision=0, out=None):
+    """The MFMA kernel with its fused 1x1 shortcut: x NHWC [B,H,W,cin], x2 NHWC [B,H,W,cin2] (read at the
+    output's stride), w [cout][kh*kw*cin + cin2] cuda f32.  Returns y (NHWC) or partial slabs."""
+    y = _conv_out(x, B, H, W, cout, kh, kw, stride, pad, nsplit, out)
+    ps, ph = (pre if pre is not None else (None, None))
+    qs, qh = (post if post is not None else (None, None))
+    rc = lib().frt_conv2d_fused(_p(x), _p(x2), _p(w), _p(y), B, H, W, cin, cin2, cout, kh, kw, stride, pad, _p(ps),
+                                _p(ph), _p(qs), _p(qh), _p(prelu), _p(res), res_hw[0], res_hw[1], epi, nsplit, tile,
+                                stream_k, precision, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc)
+    return y if nsplit > 1 else y[0]
+
+
+def conv_split_fixup(part, S, stride, B, Ho, Wo, cout, post, res=None, res_hw=(0, 0), epi=0, out=None):
+    """conv_split_fixup_kernel alone: part cuda f32 holding S slabs `stride` floats apart -> y [B,Ho,Wo,cout]."""
+    y = torch.full((B, Ho, Wo, cout), float("nan"), device=part.device) if out is None else out
+    assert y.shape == (B, Ho, Wo, cout) and y.dtype == torch.float32 and y.is_contiguous()
+    rc = lib().frt_conv_split_fixup(_p(part), S, stride, B, Ho, Wo, cout, _p(post[0]), _p(post[1]), _p(res),
+                                    res_hw[0], res_hw[1], epi, _p(y), torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc)
+    return y
 
 
 def conv2d_winograd(x, w, B, H, W, cin, cout, pre=None, post=None, prelu=None, res=None, epi=1, m=2):
