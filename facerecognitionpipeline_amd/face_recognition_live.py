@@ -10,7 +10,9 @@ which does the same for many clips (cameras) in one launch.  Whether the referen
 depends on earlier results only through "already recognised" and "attempts used up", so a recorded
 session replays exactly: the kernel gives every attempt's candidate, ``resolve_attempts`` runs at
 most ``max_attempts`` batched embed + match rounds over them, and ``process_clip`` replays the
-events through ``_update_attendance`` in (frame, detection) order.
+events through ``_update_attendance`` in (frame, detection) order.  What the reference's server
+module copied from this one (the track records, the session files, the attendance merge, the session
+close, the resolver) is in attendance_session.py; here is what is the live loop's own.
 
 Notes on parity:
 
@@ -34,15 +36,14 @@ Notes on parity:
 """
 from __future__ import annotations
 
-import json
 import os
 import types
-from collections import deque
 from datetime import datetime, timedelta
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .attendance_session import AttendanceSession, TrackRecords, _resolve, selection_key
 from .face_detection import CAPTURE_COORD_MAX, q_limit
 
 # include/frhip.h FR_LIVE_*
@@ -50,12 +51,6 @@ LIVE_MAX_FACES = 128
 LIVE_MAX_ATTEMPTS = 16
 LIVE_MAX_BUFFER = 64
 LIVE_ERR_COORD = 2
-
-
-def selection_key(det_score: float, blur_score: float) -> float:
-    """``LiveRecognitionTracker.get_best_frame``'s ``quality_score`` on plain doubles."""
-    blur_normalized = min(blur_score / 100.0, 1.0)
-    return det_score * blur_normalized
 
 
 def _two_squares(q: int) -> bool:
@@ -197,102 +192,36 @@ def resolve_attempts(track_key: Sequence, attempt, best, recognise: Callable[[Li
     ``events`` = ``{'det', 'type' ('recognized' | 'unrecognized'), 'track', 'attempt', 'best',
     'matches'}`` in detection order.  An empty ``matches`` (empty gallery) counts as an attempt and
     yields nothing, as in the reference."""
-    attempt = np.asarray(attempt).reshape(-1)
-    best = np.asarray(best).reshape(-1)
-    ev = trace.add if trace is not None else (lambda name: None)
-    recognized: Dict = {}
-    made: Dict = {}
-    log, events = [], []
-    for a in range(int(max_attempts)):
-        cand = [int(d) for d in np.flatnonzero(attempt == a) if track_key[d] not in recognized]
-        if not cand:
-            continue
-        found = recognise([int(best[d]) for d in cand])
-        for d, matches in zip(cand, found):
-            entry = {"det": d, "track": track_key[d], "attempt": a, "best": int(best[d]), "matches": list(matches)}
-            log.append(entry)
-            made[track_key[d]] = a + 1
-            if not matches:
-                continue
-            if matches[0][2] >= similarity_threshold:
-                recognized[track_key[d]] = a
-                events.append(dict(entry, type="recognized"))
-            elif a + 1 >= int(max_attempts):
-                ev("attempts_exhausted")
-                events.append(dict(entry, type="unrecognized"))
+    log, events = _resolve(range(int(max_attempts)), track_key, attempt, best, recognise, similarity_threshold,
+                           max_attempts, trace)
     if trace is not None:
-        for d in np.flatnonzero(attempt >= 0):
-            a = recognized.get(track_key[d])
-            if a is not None and a >= 1 and attempt[d] > a:
-                ev("recognized_later_then_silent")
-        for k, count in made.items():
-            if k not in recognized and count < int(max_attempts):
-                ev("unfinished_track")
-    log.sort(key=lambda e: e["det"])
-    events.sort(key=lambda e: e["det"])
+        made: Dict = {}
+        for e in log:
+            made[e["track"]] = max(made.get(e["track"], 0), e["attempt"] + 1)
+        recognized = {e["track"] for e in events if e["type"] == "recognized"}
+        if any(k not in recognized and count < int(max_attempts) for k, count in made.items()):
+            trace.add("unfinished_track")
     return log, events
 
 
-class LiveRecognitionTracker:
-    """face_recognition_live.py:18-80: what is known of every track id ever opened (ids do not come
-    back): its outcome, its attempts, a ring of its last ``buffer_size`` faces, first and last
-    timestamp."""
+class LiveRecognitionTracker(TrackRecords):
+    """face_recognition_live.py:18-80: the records of every track id ever opened (ids do not come
+    back), and the every-N-frames gate."""
 
     def __init__(self, recognition_interval=30, max_attempts=3, buffer_size=10):
-        self.recognition_interval = recognition_interval
-        self.max_attempts = max_attempts
-        self.buffer_size = buffer_size
-        self.recognized_tracks: Dict[int, Dict] = {}     # the result dict that resolved the track
-        self.recognition_attempts: Dict[int, int] = {}
-        self.track_frame_buffers: Dict[int, deque] = {}  # face dicts, oldest first
-        self.track_first_seen: Dict[int, str] = {}       # ISO timestamps
-        self.track_last_seen: Dict[int, str] = {}
+        super().__init__(recognition_interval, max_attempts, buffer_size)
 
     def should_recognize(self, track_id: int, frame_count: int) -> bool:
         resolved = track_id in self.recognized_tracks
         spent = self.recognition_attempts.get(track_id, 0) >= self.max_attempts
         return not resolved and not spent and frame_count % self.recognition_interval == 0
 
-    def add_frame(self, track_id: int, face_data: Dict, timestamp: str):
-        ring = self.track_frame_buffers.get(track_id)
-        if ring is None:
-            ring = self.track_frame_buffers[track_id] = deque(maxlen=self.buffer_size)
-            self.track_first_seen[track_id] = timestamp
-        ring.append(face_data)
-        self.track_last_seen[track_id] = timestamp
 
-    def get_best_frame(self, track_id: int) -> Optional[Dict]:
-        """The buffered face with the largest ``selection_key``; the oldest of equal keys."""
-        ring = self.track_frame_buffers.get(track_id)
-        if not ring:
-            return None
-        return max(ring, key=lambda face: selection_key(face.get("det_score", 0),
-                                                        face.get("quality_metrics", {}).get("blur_score", 0)))
-
-    def mark_recognized(self, track_id: int, student_info: Dict):
-        self.recognized_tracks[track_id] = student_info
-
-    def increment_attempts(self, track_id: int):
-        self.recognition_attempts[track_id] = 1 + self.recognition_attempts.get(track_id, 0)
-
-    def get_track_duration(self, track_id: int) -> float:
-        try:
-            first, last = self.track_first_seen[track_id], self.track_last_seen[track_id]
-        except KeyError:
-            return 0.0
-        return (datetime.fromisoformat(last) - datetime.fromisoformat(first)).total_seconds()
-
-
-class LiveFaceRecognition:
+class LiveFaceRecognition(AttendanceSession):
     """face_recognition_live.py:82-684 without the camera and the window.  ``processor`` (a
     ``FaceProcessor``, or anything with its ``process_numpy``; ``process_clip`` also needs its
     ``detector`` / ``aligner`` / ``quality_filter``), ``embedder`` and ``gallery`` default to the
     reference's settings (:114-147)."""
-
-    PROCESSOR_CONFIG = dict(output_size=112, det_size=(640, 640), det_thresh=0.5,
-                            quality_filter_config={"min_det_score": 0.5, "min_face_size": 40, "max_yaw": 60,
-                                                   "max_pitch": 45, "max_roll": 45, "check_blur": True,
-                                                   "blur_threshold": 50})
 
     def __init__(self, gallery_path="gallery/students.pkl", similarity_threshold=0.5, output_dir="sessions",
                  session_name=None, recognition_interval=30, max_recognition_attempts=3, frame_buffer_size=10,
@@ -307,27 +236,9 @@ class LiveFaceRecognition:
         self.recognition_interval = recognition_interval
         self.max_recognition_attempts = max_recognition_attempts
         self.max_distance = 100  # _simple_track_assignment's default argument
-        if processor is None:
-            from .face_recognition import FaceProcessor
-            processor = FaceProcessor(device=device, **self.PROCESSOR_CONFIG)
-        self.face_processor = processor
-        if embedder is None:
-            from .face_embedder import FaceEmbedder
-            embedder = FaceEmbedder(architecture=architecture, model_path=model_path, model_type=model_type,
-                                    device=device)
-        self.embedder = embedder
-        self.model_type = model_type
-        self.architecture = architecture
-        if gallery is None:
-            from .gallery_manager import GalleryManager
-            gallery = GalleryManager(gallery_path=gallery_path, device=self.embedder.device, verbose=verbose)
-        self.gallery = gallery
-        if hasattr(self.gallery, "attach_handle") and hasattr(self.embedder, "model"):
-            self.gallery.attach_handle(self.embedder.model)
-        num_students = len(self.gallery.get_all_students())
-        self._print(f"Loaded {num_students} enrolled students")
-        if num_students == 0:
-            self._print("\nWARNING: Gallery is empty! Please enroll students first.")
+        self._load_processor(processor, device)
+        self._load_embedder(embedder, architecture, model_path, model_type, device)
+        self._load_gallery(gallery, gallery_path)
         self.session_name = session_name or f"session_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
         self.session_dir = os.path.join(output_dir, self.session_name)
         self.perf_monitor = None
@@ -345,27 +256,13 @@ class LiveFaceRecognition:
         self._print(f"Similarity threshold: {similarity_threshold}")
         self._print("=" * 70 + "\n")
 
-    def _print(self, *args, **kw) -> None:
-        if self.verbose:
-            print(*args, **kw)
-
     def _start_session(self) -> None:
         """The session state of the constructor (:173-207): folders, tracker, counters, files."""
-        os.makedirs(self.session_dir, exist_ok=True)
-        self.tracker = LiveRecognitionTracker(recognition_interval=self.recognition_interval,
-                                              max_attempts=self.max_recognition_attempts,
-                                              buffer_size=self._frame_buffer_size)
-        self.recognized_faces_dir = os.path.join(self.session_dir, "recognized_faces")
-        self.unrecognized_faces_dir = os.path.join(self.session_dir, "unrecognized_faces")
-        os.makedirs(self.recognized_faces_dir, exist_ok=True)
-        os.makedirs(self.unrecognized_faces_dir, exist_ok=True)
-        self.session_start = datetime.now()
-        self.frame_count = 0
-        self.total_faces_detected = 0
-        self.total_recognition_attempts = 0
         self.active_tracks: Dict[int, Dict] = {}
         self.next_track_id = 0
-        self._init_session_files()
+        self._open_session(LiveRecognitionTracker(recognition_interval=self.recognition_interval,
+                                                  max_attempts=self.max_recognition_attempts,
+                                                  buffer_size=self._frame_buffer_size))
 
     def _camera(self, index: int) -> "LiveFaceRecognition":
         """A session of its own under ``session_dir/camera_%02d`` that shares the models."""
@@ -376,43 +273,6 @@ class LiveFaceRecognition:
         cam.cameras = [cam]
         cam._start_session()
         return cam
-
-    # -- the session files (:209-247) ----------------------------------------------------
-    def _init_session_files(self):
-        session_data = {
-            "session_id": self.session_name,
-            "start_time": self.session_start.isoformat(),
-            "end_time": None,
-            "status": "active",
-            "settings": {
-                "similarity_threshold": self.similarity_threshold,
-                "recognition_interval": self.recognition_interval,
-                "max_recognition_attempts": self.max_recognition_attempts,
-            },
-            "statistics": {
-                "total_frames_processed": 0,
-                "total_faces_detected": 0,
-                "total_recognition_attempts": 0,
-                "unique_students_recognized": 0,
-                "unrecognized_tracks": 0,
-            },
-        }
-        attendance_data = {
-            "session_id": self.session_name,
-            "last_updated": datetime.now().isoformat(),
-            "recognized": [],
-            "unrecognized": [],
-        }
-        self._write_session(session_data)
-        self._write_attendance(attendance_data)
-
-    def _write_session(self, data: Dict):
-        with open(os.path.join(self.session_dir, "session.json"), "w") as f:
-            json.dump(data, f, indent=2)
-
-    def _write_attendance(self, data: Dict):
-        with open(os.path.join(self.session_dir, "attendance.json"), "w") as f:
-            json.dump(data, f, indent=2)
 
     # -- the per-frame flow (:249-414) ------------------------------------------------------
     def _simple_track_assignment(self, faces: List[Dict], max_distance=None):
@@ -441,29 +301,11 @@ class LiveFaceRecognition:
         self.active_tracks = {t: dict(entry) for t, entry in assigned.items()}
         return assigned
 
-    def _result_of(self, matches, track_id: int, det_score, blur_score, timestamp: str) -> Optional[Dict]:
-        """The result dict of ``_recognize_face`` (:296-318) from ``gallery.search``'s list."""
-        if len(matches) == 0:
-            return None
-        student_id, name, score = matches[0]
-        return {
-            "student_id": student_id,
-            "name": name,
-            "confidence": float(score),
-            "track_id": track_id,
-            "recognized": bool(score >= self.similarity_threshold),
-            "top_matches": [{"student_id": sid, "name": n, "score": float(s)} for sid, n, s in matches],
-            "timestamp": timestamp,
-            "detection_quality": {"det_score": float(det_score), "blur_score": blur_score},
-        }
-
     def _recognize_face(self, face_data: Dict, track_id: int, timestamp: Optional[str] = None) -> Optional[Dict]:
         self.total_recognition_attempts += 1
         embedding = self.embedder.extract_embedding(face_data["aligned_face"], normalize=True)
         results = self.gallery.search(embedding, top_k=3)
-        return self._result_of(results, track_id, face_data["det_score"],
-                               face_data["quality_metrics"].get("blur_score", 0),
-                               timestamp or datetime.now().isoformat())
+        return self._result_of(results, track_id, face_data, timestamp or datetime.now().isoformat())
 
     def _settle(self, track_id: int, result: Optional[Dict], aligned_face, original_crop,
                 events: List[tuple]) -> None:
@@ -534,73 +376,16 @@ class LiveFaceRecognition:
             Image.fromarray(np.ascontiguousarray(original_crop, dtype=np.uint8)).save(filepath_original, quality=95)
         return filepath_aligned
 
-    def _update_attendance(self, events: List[tuple]):
-        """:458-506: merge a frame's ``(type, result)`` events into ``attendance.json``.  A student is
-        listed once; a later track that recognises the same student only raises the entry's confidence
-        (and the detection quality that goes with it)."""
-        with open(os.path.join(self.session_dir, "attendance.json"), "r") as f:
-            attendance = json.load(f)
-        recognized, unrecognized = attendance["recognized"], attendance["unrecognized"]
-        note = self.trace.add if self.trace is not None else (lambda name: None)
-        for kind, result in events:
-            tid = result["track_id"]
-            label = f"track_{tid:04d}"
-            first_seen = self.tracker.track_first_seen.get(tid, result["timestamp"])
-            duration = self.tracker.get_track_duration(tid)
-            saved = result.get("saved_face_path", "")
-            if kind == "recognized":
-                known = [s for s in recognized if s["student_id"] == result["student_id"]]
-                if not known:
-                    recognized.append({"student_id": result["student_id"], "name": result["name"],
-                                       "first_seen": first_seen, "confidence": result["confidence"], "track_id": label,
-                                       "duration_seconds": duration, "detection_quality": result["detection_quality"],
-                                       "saved_face_path": saved})
-                elif result["confidence"] > known[0]["confidence"]:
-                    known[0].update(confidence=result["confidence"], detection_quality=result["detection_quality"])
-                    note("second_track_higher")
-                else:
-                    note("second_track_lower")
-            elif kind == "unrecognized":
-                best_match = {key: result[key] for key in ("name", "student_id", "confidence")}
-                unrecognized.append({"track_id": label, "first_seen": first_seen, "duration_seconds": duration,
-                                     "best_match": best_match, "reason": "below_threshold",
-                                     "threshold": self.similarity_threshold,
-                                     "attempts": self.tracker.recognition_attempts.get(tid, 0),
-                                     "top_matches": result["top_matches"], "saved_face_path": saved})
-        attendance["last_updated"] = datetime.now().isoformat()
-        self._write_attendance(attendance)
+    def _rate_statistics(self, seconds: float) -> Dict:
+        return {"average_fps": self.frame_count / seconds if seconds > 0 else 0}
+
+    def _rate_summary(self, statistics: Dict) -> str:
+        return f"\nAverage FPS: {statistics['average_fps']:.1f}"
 
     def _finalize_session(self):
-        """:632-684: close ``session.json`` (end time, status, duration, the statistics) and return it."""
-        ended = datetime.now()
-        seconds = (ended - self.session_start).total_seconds()
-        with open(os.path.join(self.session_dir, "session.json"), "r") as f:
-            session = json.load(f)
-        with open(os.path.join(self.session_dir, "attendance.json"), "r") as f:
-            attendance = json.load(f)
-        session.update(end_time=ended.isoformat(), status="completed", duration_seconds=seconds)
-        session["statistics"] = {
-            "total_frames_processed": self.frame_count,
-            "total_faces_detected": self.total_faces_detected,
-            "total_recognition_attempts": self.total_recognition_attempts,
-            "unique_students_recognized": len(attendance["recognized"]),
-            "unrecognized_tracks": len(attendance["unrecognized"]),
-            "average_fps": self.frame_count / seconds if seconds > 0 else 0,
-        }
-        self._write_session(session)
-        rule = "=" * 70
-        self._print(f"\n{rule}\nFINALIZING SESSION\n{rule}")
-        self._print(f"\nSession: {self.session_name}\nDuration: {seconds:.1f} seconds\n"
-                    f"Frames processed: {self.frame_count}\nAverage FPS: {session['statistics']['average_fps']:.1f}")
-        self._print(f"\nRecognized students: {len(attendance['recognized'])}")
-        for s in attendance["recognized"]:
-            self._print(f"{s['name']} ({s['student_id']}) - confidence: {s['confidence']:.3f}")
-        self._print(f"\nUnrecognized tracks: {len(attendance['unrecognized'])}")
-        for t in attendance["unrecognized"]:
-            best = t["best_match"]
-            self._print(f"{t['track_id']} - best match: {best['name']} ({best['confidence']:.3f})")
-        self._print(f"\nOutput directory: {self.session_dir}\n{rule}\n")
-        return session
+        """:632-684: close ``session.json`` (end time, status, duration, the statistics with the frame
+        rate) and return it."""
+        return self._close_session()
 
     # -- a recorded clip, or one per camera -----------------------------------------------------
     def process_clip(self, frames, timestamps=None, fps: float = 30.0):
@@ -709,8 +494,7 @@ class LiveFaceRecognition:
                 tr.track_last_seen[tid] = ts[f]  # the duration an event reports ends at its frame
                 tr.increment_attempts(tid)
                 face = faces[e["best"]]
-                result = cam._result_of(e["matches"], tid, face["det_score"],
-                                        face["quality_metrics"].get("blur_score", 0), ts[f])
+                result = cam._result_of(e["matches"], tid, face, ts[f])
                 if e["det"] in my_events:
                     x1, y1, x2, y2 = map(int, face["bbox"])
                     original = rgb[int(det_frame[e["best"]]) - f0, y1:y2, x1:x2].cpu().numpy()

@@ -6,9 +6,10 @@ The server's tracker is not the live loop's (face_recognition_live.py): it has n
 (``recognition_interval`` is stored and never read), it gates on the detection score of the best
 buffered face, it has a wall-clock retry cooldown that resets the attempts and empties the ring, and
 its track ids come from outside: the client's in ``process_faces``, a fresh one per face in
-``process_full_frame``.  What it shares with the live loop is that an attempt depends on earlier
-recognition results only through "this track is already recognised"; everything else follows from the
-detections and the clock.  So a recorded log replays exactly: ``fr_server_tracks`` (contract:
+``process_full_frame``.  What it shares with the live loop's is in attendance_session.py
+(``TrackRecords``), as is the shared part of the two session classes (``AttendanceSession``) and of the
+two resolvers.  The two flows also share that an attempt depends on earlier recognition results only
+through "this track is already recognised"; everything else follows from the detections and the clock.  So a recorded log replays exactly: ``fr_server_tracks`` (contract:
 ``server_tracks_host``) decides every track's attempts in one launch, ``resolve_server_attempts``
 embeds and matches them an ordinal at a time, and ``process_requests`` / ``process_frames`` replay the
 bookkeeping in request order.
@@ -42,17 +43,15 @@ from __future__ import annotations
 import argparse
 import base64
 import io
-import json
 import math
 import os
 import time
-from collections import deque
 from datetime import datetime
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .face_recognition_live import selection_key
+from .attendance_session import AttendanceSession, TrackRecords, _resolve, selection_key
 
 # include/frhip.h FR_SERVER_*
 SERVER_MAX_ATTEMPTS = 16
@@ -197,62 +196,23 @@ def resolve_server_attempts(track_key: Sequence, attempt, best, recognise: Calla
     made, ``{'det', 'track', 'attempt', 'best', 'matches'}``; ``events`` = the same with ``'type'``
     ('recognized' | 'unrecognized'); both in detection order, which is request order, then face order.
     An empty ``matches`` (empty gallery) counts as an attempt and yields nothing, as in the reference."""
-    attempt = np.asarray(attempt).reshape(-1)
-    best = np.asarray(best).reshape(-1)
-    max_attempts = int(max_attempts)
-    ev = trace.add if trace is not None else (lambda name: None)
-    recognized: Dict = {}
-    log, events = [], []
-    by_ordinal: Dict[int, List[int]] = {}
-    for d in np.flatnonzero(attempt >= 0):
-        by_ordinal.setdefault(int(attempt[d]), []).append(int(d))
-    for k in sorted(by_ordinal):
-        cand = [d for d in by_ordinal[k] if track_key[d] not in recognized]
-        if not cand:
-            continue
-        found = recognise([int(best[d]) for d in cand])
-        for d, matches in zip(cand, found):
-            entry = {"det": d, "track": track_key[d], "attempt": k, "best": int(best[d]), "matches": list(matches)}
-            log.append(entry)
-            if not matches:
-                continue
-            if matches[0][2] >= similarity_threshold:
-                recognized[track_key[d]] = k
-                events.append(dict(entry, type="recognized"))
-            elif k % max_attempts == max_attempts - 1:
-                ev("attempts_exhausted")
-                if k >= max_attempts:
-                    ev("second_cycle_unrecognized")
-                events.append(dict(entry, type="unrecognized"))
-    if trace is not None:
-        for d in np.flatnonzero(attempt >= 0):
-            k = recognized.get(track_key[d])
-            if k is not None and k >= 1 and attempt[d] > k:
-                ev("recognized_later_then_silent")
-    log.sort(key=lambda e: e["det"])
-    events.sort(key=lambda e: e["det"])
-    return log, events
+    ordinals = np.unique(np.asarray(attempt).reshape(-1))
+    return _resolve([int(k) for k in ordinals if k >= 0], track_key, attempt, best, recognise, similarity_threshold,
+                    max_attempts, trace)
 
 
-class LiveRecognitionTracker:
-    """face_recognition_server.py:23-124: what is known of every track id ever seen: its outcome, the
-    attempts of its current cycle, a ring of its last ``buffer_size`` faces, first and last timestamp,
-    and the deadline of its retry cooldown.  ``clock`` returns seconds (default ``time.time``); every
-    method that needs the time also takes it as ``now``."""
+class LiveRecognitionTracker(TrackRecords):
+    """face_recognition_server.py:23-124: the records of every track id ever seen (the attempts are
+    those of the current cycle), and the deadline of its retry cooldown.  ``recognition_interval`` is
+    stored; ``should_recognize`` does not read it.  ``clock`` returns seconds (default ``time.time``);
+    every method that needs the time also takes it as ``now``."""
 
     def __init__(self, recognition_interval=30, max_attempts=3, buffer_size=10, retry_cooldown=10.0,
                  clock: Callable[[], float] = time.time):
-        self.recognized_tracks: Dict = {}      # track id -> the result dict that resolved it
-        self.recognition_attempts: Dict = {}   # track id -> attempts of the current cycle
-        self.track_frame_buffers: Dict = {}    # track id -> deque of face dicts, oldest first
-        self.track_first_seen: Dict = {}       # ISO timestamps
-        self.track_last_seen: Dict = {}
+        super().__init__(recognition_interval, max_attempts, buffer_size)
         self.track_last_attempt: Dict = {}
         self.client_tracks: Dict = {}          # never written (the reference's writer is commented out)
         self.track_cooldowns: Dict = {}        # track id -> deadline in clock seconds
-        self.recognition_interval = recognition_interval  # stored; should_recognize does not read it
-        self.max_attempts = max_attempts
-        self.buffer_size = buffer_size
         self.retry_cooldown = retry_cooldown
         self.clock = clock
 
@@ -268,35 +228,9 @@ class LiveRecognitionTracker:
         face = self.get_best_frame(track_id)
         return face is not None and face.get("det_score", 0) > DET_GATE
 
-    def add_frame(self, track_id, face_data: Dict, timestamp: str):
-        ring = self.track_frame_buffers.get(track_id)
-        if ring is None:
-            ring = self.track_frame_buffers[track_id] = deque(maxlen=self.buffer_size)
-            self.track_first_seen[track_id] = timestamp
-        self.track_last_seen[track_id] = timestamp
-        ring.append(face_data)
-
-    def get_best_frame(self, track_id) -> Optional[Dict]:
-        """The buffered face with the largest ``selection_key``; the oldest of equal keys."""
-        ring = self.track_frame_buffers.get(track_id)
-        if not ring:
-            return None
-        return max(ring, key=lambda face: selection_key(face.get("det_score", 0),
-                                                        face.get("quality_metrics", {}).get("blur_score", 0)))
-
-    def mark_recognized(self, track_id, student_info: Dict):
-        self.recognized_tracks[track_id] = student_info
-
     def increment_attempts(self, track_id):
-        self.recognition_attempts[track_id] = 1 + self.recognition_attempts.get(track_id, 0)
+        super().increment_attempts(track_id)
         self.track_last_attempt[track_id] = datetime.now().isoformat()
-
-    def get_track_duration(self, track_id) -> float:
-        try:
-            first, last = self.track_first_seen[track_id], self.track_last_seen[track_id]
-        except KeyError:
-            return 0.0
-        return (datetime.fromisoformat(last) - datetime.fromisoformat(first)).total_seconds()
 
     def is_track_in_cooldown(self, track_id, now: Optional[float] = None) -> bool:
         """True before the deadline.  At or past it the cooldown ends: the attempts go to 0 and the
@@ -339,17 +273,14 @@ def decode_image(data: bytes) -> np.ndarray:
         return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
 
 
-class FaceRecognitionServer:
+class FaceRecognitionServer(AttendanceSession):
     """face_recognition_server.py:126-840.  ``processor`` (a ``FaceProcessor``, or anything with its
     ``process_numpy``; ``process_frames`` also needs ``process_images``), ``embedder`` and ``gallery``
     default to the reference's settings (:155-200).  With a ``FaceEmbedder`` and a ``GalleryManager``
     the due faces of a request are embedded and matched in one ``fr_embed_match``; stand-ins that only
     have ``extract_embedding`` / ``search`` are asked face by face."""
 
-    PROCESSOR_CONFIG = dict(output_size=112, det_size=(640, 640), det_thresh=0.5,
-                            quality_filter_config={"min_det_score": 0.5, "min_face_size": 40, "max_yaw": 60,
-                                                   "max_pitch": 45, "max_roll": 45, "check_blur": True,
-                                                   "blur_threshold": 50})
+    SUMMARY_INDENT = "  "
 
     def __init__(self, gallery_path="gallery/students.pkl", similarity_threshold=0.5, output_dir="sessions",
                  session_name=None, require_session_name=False, recognition_interval=30, max_recognition_attempts=3,
@@ -372,30 +303,12 @@ class FaceRecognitionServer:
         self.retry_cooldown = retry_cooldown  # _create_session builds the tracker without one: 10.0
         self.clock = clock
         _check_settings(max_recognition_attempts, frame_buffer_size, retry_cooldown)
-        if embedder is None:
-            from .face_embedder import FaceEmbedder
-            embedder = FaceEmbedder(architecture=architecture, model_path=model_path, model_type=model_type,
-                                    device=device)
-        self.embedder = embedder
-        self.model_type = model_type
-        self.architecture = architecture
-        if processor is None:
-            from .face_recognition import FaceProcessor
-            processor = FaceProcessor(device=device, **self.PROCESSOR_CONFIG)
-        self.face_processor = processor
+        self._load_embedder(embedder, architecture, model_path, model_type, device)
+        self._load_processor(processor, device)
         self.high_quality_crop_size = 600
         self.max_tracking_distance = 100
         self.next_track_id = 0
-        if gallery is None:
-            from .gallery_manager import GalleryManager
-            gallery = GalleryManager(gallery_path=gallery_path, device=self.embedder.device, verbose=verbose)
-        self.gallery = gallery
-        if hasattr(self.gallery, "attach_handle") and hasattr(self.embedder, "model"):
-            self.gallery.attach_handle(self.embedder.model)
-        num_students = len(self.gallery.get_all_students())
-        self._print(f"Loaded {num_students} enrolled students")
-        if num_students == 0:
-            self._print("\nWARNING: Gallery is empty! Please enroll students first.")
+        self._load_gallery(gallery, gallery_path)
         self.session_name = None
         self.session_dir = None
         self.session_start = None
@@ -417,72 +330,19 @@ class FaceRecognitionServer:
             self._print(f"Similarity threshold: {similarity_threshold}")
             self._print("=" * 70 + "\n")
 
-    def _print(self, *args, **kw) -> None:
-        if self.verbose:
-            print(*args, **kw)
-
-    def _note(self, name: str) -> None:
-        if self.trace is not None:
-            self.trace.add(name)
-
-    # -- the session and its files (:230-312) ------------------------------------------------
+    # -- the session (:230-262) ----------------------------------------------------------------
     def _create_session(self, session_name: str):
         self.session_name = session_name
         self.session_dir = os.path.join(self.output_dir, self.session_name)
-        os.makedirs(self.session_dir, exist_ok=True)
-        self.tracker = LiveRecognitionTracker(recognition_interval=self.recognition_interval,
-                                              max_attempts=self.max_recognition_attempts,
-                                              buffer_size=self.frame_buffer_size, retry_cooldown=self.retry_cooldown,
-                                              clock=self.clock)
-        self.recognized_faces_dir = os.path.join(self.session_dir, "recognized_faces")
-        self.unrecognized_faces_dir = os.path.join(self.session_dir, "unrecognized_faces")
+        self._open_session(LiveRecognitionTracker(recognition_interval=self.recognition_interval,
+                                                  max_attempts=self.max_recognition_attempts,
+                                                  buffer_size=self.frame_buffer_size,
+                                                  retry_cooldown=self.retry_cooldown, clock=self.clock))
         self.snapshots_dir = os.path.join(self.session_dir, "snapshots")
-        for d in (self.recognized_faces_dir, self.unrecognized_faces_dir, self.snapshots_dir):
-            os.makedirs(d, exist_ok=True)
-        self.session_start = datetime.now()
-        self.frame_count = 0
-        self.total_faces_detected = 0
-        self.total_recognition_attempts = 0
-        self._init_session_files()
+        os.makedirs(self.snapshots_dir, exist_ok=True)
         self._print("\n" + "=" * 70)
         self._print(f"Session created: {self.session_name}\nOutput: {self.session_dir}")
         self._print("=" * 70 + "\n")
-
-    def _init_session_files(self):
-        session_data = {
-            "session_id": self.session_name,
-            "start_time": self.session_start.isoformat(),
-            "end_time": None,
-            "status": "active",
-            "settings": {
-                "similarity_threshold": self.similarity_threshold,
-                "recognition_interval": self.recognition_interval,
-                "max_recognition_attempts": self.max_recognition_attempts,
-            },
-            "statistics": {
-                "total_frames_processed": 0,
-                "total_faces_detected": 0,
-                "total_recognition_attempts": 0,
-                "unique_students_recognized": 0,
-                "unrecognized_tracks": 0,
-            },
-        }
-        attendance_data = {
-            "session_id": self.session_name,
-            "last_updated": datetime.now().isoformat(),
-            "recognized": [],
-            "unrecognized": [],
-        }
-        self._write_session(session_data)
-        self._write_attendance(attendance_data)
-
-    def _write_session(self, data: Dict):
-        with open(os.path.join(self.session_dir, "session.json"), "w") as f:
-            json.dump(data, f, indent=2)
-
-    def _write_attendance(self, data: Dict):
-        with open(os.path.join(self.session_dir, "attendance.json"), "w") as f:
-            json.dump(data, f, indent=2)
 
     # -- recognition (:314-347) ------------------------------------------------------------------
     @staticmethod
@@ -503,22 +363,6 @@ class FaceRecognitionServer:
             return self.gallery.match_resolved(len(crops), 3,
                                                lambda h, k, idx, score: h.embed_match(rgb, k, idx, score))
         return [self.gallery.search(self.embedder.extract_embedding(c, normalize=True), top_k=3) for c in crops]
-
-    def _result_of(self, matches, track_id, face_data: Dict, timestamp: str) -> Optional[Dict]:
-        if len(matches) == 0:
-            return None
-        student_id, name, score = matches[0]
-        return {
-            "student_id": student_id,
-            "name": name,
-            "confidence": float(score),
-            "track_id": track_id,
-            "recognized": bool(score >= self.similarity_threshold),
-            "top_matches": [{"student_id": sid, "name": n, "score": float(s)} for sid, n, s in matches],
-            "timestamp": timestamp,
-            "detection_quality": {"det_score": float(face_data["det_score"]),
-                                  "blur_score": face_data["quality_metrics"].get("blur_score", 0)},
-        }
 
     def _recognize_face(self, face_data: Dict, track_id, timestamp: Optional[str] = None) -> Optional[Dict]:
         self.total_recognition_attempts += 1
@@ -651,42 +495,6 @@ class FaceRecognitionServer:
                 f.write(base64.b64decode(original_crop_base64))
         return stem + "_aligned.png"
 
-    def _update_attendance(self, events: List[tuple]):
-        """:478-526: merge a request's ``(type, result)`` events into ``attendance.json``.  A student is
-        listed once; a later track that recognises the same student only raises the entry's confidence
-        (and the detection quality that goes with it).  A track may be listed as unrecognized once per
-        cooldown cycle."""
-        with open(os.path.join(self.session_dir, "attendance.json"), "r") as f:
-            attendance = json.load(f)
-        recognized, unrecognized = attendance["recognized"], attendance["unrecognized"]
-        for kind, result in events:
-            tid = result["track_id"]
-            label = f"track_{tid:04d}"
-            first_seen = self.tracker.track_first_seen.get(tid, result["timestamp"])
-            duration = self.tracker.get_track_duration(tid)
-            saved = result.get("saved_face_path", "")
-            if kind == "recognized":
-                known = [s for s in recognized if s["student_id"] == result["student_id"]]
-                if not known:
-                    recognized.append({"student_id": result["student_id"], "name": result["name"],
-                                       "first_seen": first_seen, "confidence": result["confidence"], "track_id": label,
-                                       "duration_seconds": duration, "detection_quality": result["detection_quality"],
-                                       "saved_face_path": saved})
-                elif result["confidence"] > known[0]["confidence"]:
-                    known[0].update(confidence=result["confidence"], detection_quality=result["detection_quality"])
-                    self._note("second_track_higher")
-                else:
-                    self._note("second_track_lower")
-            elif kind == "unrecognized":
-                best_match = {key: result[key] for key in ("name", "student_id", "confidence")}
-                unrecognized.append({"track_id": label, "first_seen": first_seen, "duration_seconds": duration,
-                                     "best_match": best_match, "reason": "below_threshold",
-                                     "threshold": self.similarity_threshold,
-                                     "attempts": self.tracker.recognition_attempts.get(tid, 0),
-                                     "top_matches": result["top_matches"], "saved_face_path": saved})
-        attendance["last_updated"] = datetime.now().isoformat()
-        self._write_attendance(attendance)
-
     def save_snapshot(self, snapshot_base64: str, frame_count: int, timestamp: str) -> str:
         filepath = os.path.join(self.snapshots_dir, f"snapshot_frame_{frame_count:06d}_{timestamp}.png")
         with open(filepath, "wb") as f:
@@ -697,34 +505,7 @@ class FaceRecognitionServer:
         """:538-584: close ``session.json`` (end time, status, duration, the statistics) and return it
         (the reference returns nothing).  ``client_report`` went to the performance monitor and is
         ignored."""
-        ended = datetime.now()
-        seconds = (ended - self.session_start).total_seconds()
-        with open(os.path.join(self.session_dir, "session.json"), "r") as f:
-            session = json.load(f)
-        with open(os.path.join(self.session_dir, "attendance.json"), "r") as f:
-            attendance = json.load(f)
-        session.update(end_time=ended.isoformat(), status="completed", duration_seconds=seconds)
-        session["statistics"] = {
-            "total_frames_processed": self.frame_count,
-            "total_faces_detected": self.total_faces_detected,
-            "total_recognition_attempts": self.total_recognition_attempts,
-            "unique_students_recognized": len(attendance["recognized"]),
-            "unrecognized_tracks": len(attendance["unrecognized"]),
-        }
-        self._write_session(session)
-        rule = "=" * 70
-        self._print(f"\n{rule}\nFINALIZING SESSION\n{rule}")
-        self._print(f"\nSession: {self.session_name}\nDuration: {seconds:.1f} seconds\n"
-                    f"Frames processed: {self.frame_count}")
-        self._print(f"\nRecognized students: {len(attendance['recognized'])}")
-        for s in attendance["recognized"]:
-            self._print(f"  {s['name']} ({s['student_id']}) - confidence: {s['confidence']:.3f}")
-        self._print(f"\nUnrecognized tracks: {len(attendance['unrecognized'])}")
-        for t in attendance["unrecognized"]:
-            best = t["best_match"]
-            self._print(f"  {t['track_id']} - best match: {best['name']} ({best['confidence']:.3f})")
-        self._print(f"\nOutput directory: {self.session_dir}\n{rule}\n")
-        return session
+        return self._close_session()
 
     # -- whole frames (:586-823) -------------------------------------------------------------------
     def _high_quality_crop(self, frame_rgb: np.ndarray, bbox) -> np.ndarray:

@@ -68,7 +68,8 @@ def test_host_statement_reproduces_the_fixture_and_the_fixture_reaches_every_cas
             for e in (e for e in events if frame_of[e["det"]] == f):
                 m = s["metrics"][e["best"]]
                 live.tracker.recognition_attempts[e["track"]] = e["attempt"] + 1
-                result = live._result_of(e["matches"], e["track"], m[0], float(m[1]), "2026-01-01T00:00:00")
+                face_data = {"det_score": m[0], "quality_metrics": {"blur_score": float(m[1])}}
+                result = live._result_of(e["matches"], e["track"], face_data, "2026-01-01T00:00:00")
                 frame_events.append((e["type"], result))
             live._update_attendance(frame_events)
         assert LC.strip(json.loads((tmp_path / f"live_{k}" / "attendance.json").read_text())) == s["attendance"], k
