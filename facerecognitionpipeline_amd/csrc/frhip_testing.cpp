@@ -224,13 +224,16 @@ int frt_set_wino4_poll_limit(int n) {
   g_knobs.wino4_poll = n < 0 ? WINO4_POLL_DEFAULT : n;
   return FR_OK;
 }
-int frt_conv2d_small(const float* x, const float* x2, const float* w, float* y, int B, int H, int W, int cin,
+int frt_conv2d_small_ex(const float* x, const float* x2, const float* w, float* y, int B, int H, int W, int cin,
                      int cin2, int cout, int stride, const float* pre_scale, const float* pre_shift,
                      const float* post_scale, const float* post_shift, const float* prelu, const float* res, int epi,
-                     void* stream) {
-  if (B < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2) || epi < 0 || epi > 3 || cin2 < 0 ||
-      ((pre_scale != nullptr) != (epi == EPI_AFFINE_PRELU)) || (pre_scale && !pre_shift))
-    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_small: bad arguments");
+                     int blk, float* y2, const float* y2_scale, const float* y2_shift, void* stream) {
+  // Only what conv_shape and the weight reorder below need, and a pre-BN pointer pair the kernel
+  // would dereference, are checked here: which epilogues take pre-BN, the shortcut's width and
+  // pointer, the residual, y2's operands are launch_convs' refusals, so tests pin the launcher's.
+  if (B < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2) || cin < 16 || cout < 16 || cin2 < 0 ||
+      ((pre_scale != nullptr) != (pre_shift != nullptr)) || !w || cout % 16 || cin % 16 || cin2 % 16)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_small_ex: bad arguments");
   ConvW cw;
   cw.geometry(cin, cout, 3, 3, stride, 1);
   cw.cin2 = cin2;
@@ -247,8 +250,10 @@ int frt_conv2d_small(const float* x, const float* x2, const float* w, float* y, 
   p.res = res;
   p.res_H = H;
   p.res_W = W;
-  if (!w || cout % 16 || cin % 16 || cin2 % 16)
-    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_small: bad arguments");
+  p.blk = blk;
+  p.y2 = y2;
+  p.y2_scale = y2_scale;
+  p.y2_shift = y2_shift;
   // the kernel reads its filters in fragment order: a temporary copy (test entry point)
   float* wf = nullptr;
   const size_t wbytes = (size_t)cout * (9 * cin + cin2) * sizeof(float);
@@ -263,8 +268,16 @@ int frt_conv2d_small(const float* x, const float* x2, const float* w, float* y, 
     (void)hipFree(wf);
     if (e == hipSuccess) e = e2;
   }
-  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_small: ") + hipGetErrorString(e));
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_small_ex: refused");
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_small_ex: ") + hipGetErrorString(e));
   return FR_OK;
+}
+int frt_conv2d_small(const float* x, const float* x2, const float* w, float* y, int B, int H, int W, int cin,
+                     int cin2, int cout, int stride, const float* pre_scale, const float* pre_shift,
+                     const float* post_scale, const float* post_shift, const float* prelu, const float* res, int epi,
+                     void* stream) {
+  return frt_conv2d_small_ex(x, x2, w, y, B, H, W, cin, cin2, cout, stride, pre_scale, pre_shift, post_scale,
+                             post_shift, prelu, res, epi, 0, nullptr, nullptr, nullptr, stream);
 }
 int frt_set_small_conv(fr_handle* h, int max_n) {
   return set_handle_knob(h, [&] { h->convs_max_n = std::max(0, max_n); });
@@ -290,9 +303,10 @@ int frt_set_wino4_split(int on) {
   return FR_OK;
 }
 
-int frt_conv2d_winograd4(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout,
-                        const float* pre_scale, const float* pre_shift, const float* post_scale,
-                        const float* post_shift, const float* prelu, const float* res, int epi, void* stream) {
+int frt_conv2d_winograd4_ex(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout,
+                           const float* pre_scale, const float* pre_shift, const float* post_scale,
+                           const float* post_shift, const float* prelu, const float* res, int epi, int blk,
+                           void* stream) {
   // epilogues: the IR body's (1 with pre-BN, 2) and the detector's (0, 1 without pre-BN, 5)
   const bool res_epi = epi == EPI_AFFINE_RES || epi == EPI_AFFINE_RES_PRELU;
   const bool prelu_epi = epi == EPI_AFFINE_PRELU || epi == EPI_AFFINE_RES_PRELU;
@@ -300,7 +314,7 @@ int frt_conv2d_winograd4(const float* x, const float* w, float* y, int B, int H,
       (epi != EPI_AFFINE && epi != EPI_AFFINE_PRELU && epi != EPI_AFFINE_RES && epi != EPI_AFFINE_RES_PRELU) ||
       (pre_scale && (epi != EPI_AFFINE_PRELU || !pre_shift)) || (prelu_epi && !prelu) || (res_epi != (res != nullptr)) ||
       !post_scale || !post_shift || B < 1 || H < 1 || W < 1)
-    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_winograd4: bad arguments");
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_winograd4_ex: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   ConvW cw;
   cw.cin = cin;
@@ -308,10 +322,10 @@ int frt_conv2d_winograd4(const float* x, const float* w, float* y, int B, int H,
   cw.pre_shift = const_cast<float*>(pre_shift);
   std::vector<float> t;
   if (hipStreamSynchronize(s) != hipSuccess || !wino4_pre_fold(&cw, t))
-    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_winograd4: pre-BN scale has a zero");
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_conv2d_winograd4_ex: pre-BN scale has a zero");
   float *u = nullptr, *part = nullptr, *pre_t = nullptr;
   if (hipMalloc((void**)&u, (wino4_weight_floats(cout, cin) + cin) * sizeof(float)) != hipSuccess)
-    return fail(nullptr, FR_ERR_HIP, "frt_conv2d_winograd4: allocation failed");
+    return fail(nullptr, FR_ERR_HIP, "frt_conv2d_winograd4_ex: allocation failed");
   pre_t = u + wino4_weight_floats(cout, cin);
   hipError_t e = hipMemcpy(pre_t, t.data(), cin * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = launch_wino4_weights(w, pre_scale, u, cout, cin, s);
@@ -337,6 +351,7 @@ int frt_conv2d_winograd4(const float* x, const float* w, float* y, int B, int H,
     p.poll_max = g_knobs.wino4_poll > 0 ? g_knobs.wino4_poll : -1;
     p.err = frt_err;
     p.shapes = g_knobs.wino4_shapes;
+    p.blk = blk;
     if (g_frt_wino4_split) {  // split-K partial slots (64 KiB each)
       p.part_floats = 257ll * 2 * 16 * 16 * 64;
       if (hipMalloc((void**)&part, p.part_floats * sizeof(float)) != hipSuccess) e = hipErrorOutOfMemory;
@@ -348,16 +363,35 @@ int frt_conv2d_winograd4(const float* x, const float* w, float* y, int B, int H,
   (void)hipFree(u);
   (void)hipFree(part);
   if (e == hipSuccess) e = se;
-  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_winograd4: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_conv2d_winograd4_ex: ") + hipGetErrorString(e));
   if (*(volatile int*)frt_err & FR_DEVERR_W4_HANDOFF)
-    return fail(nullptr, FR_ERR_HIP, "frt_conv2d_winograd4: F(4x4) ring hand-off timed out in wino4_kernel");
+    return fail(nullptr, FR_ERR_HIP, "frt_conv2d_winograd4_ex: F(4x4) ring hand-off timed out in wino4_kernel");
   return FR_OK;
+}
+
+int frt_conv2d_winograd4(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout,
+                         const float* pre_scale, const float* pre_shift, const float* post_scale,
+                         const float* post_shift, const float* prelu, const float* res, int epi, void* stream) {
+  return frt_conv2d_winograd4_ex(x, w, y, B, H, W, cin, cout, pre_scale, pre_shift, post_scale, post_shift, prelu, res,
+                                 epi, 0, stream);
 }
 
 int frt_stem(const uint8_t* img, int B, const float* lut, const float* w27x64, const float* bn_scale,
              const float* bn_shift, const float* prelu, float* y, void* stream) {
   hipError_t e = launch_stem(img, B, lut, w27x64, bn_scale, bn_shift, prelu, y, (hipStream_t)stream);
   if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_stem: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_head_reduce(const float* partial, int nsplit, long long split_stride, const float* fc_bias,
+                    const float* bn_scale, const float* bn_shift, float* emb, int n, int normalize, int model_l2,
+                    void* stream) {
+  if (!partial || !fc_bias || !bn_scale || !bn_shift || !emb || n < 1 || nsplit < 1 ||
+      split_stride < (long long)n * 512)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_head_reduce: bad arguments");
+  const hipError_t e = launch_head_reduce(partial, nsplit, split_stride, fc_bias, bn_scale, bn_shift, emb, n,
+                                          normalize != 0, model_l2 != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_head_reduce: ") + hipGetErrorString(e));
   return FR_OK;
 }
 

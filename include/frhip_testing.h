@@ -61,7 +61,9 @@ int frt_conv2d_winograd(const float* x, const float* w, float* y, int B, int H, 
 /* Winograd F(4x4,3x3) (the FR_CONV_WINOGRAD4 path, conv_winograd4.hip), same arguments;
  * cin % 16 == 0, cout % 16 == 0; epi also 0 (affine) and 5 (affine + residual + PReLU), and 1 without
  * pre-BN (the detector's convs).  frt_conv2d_winograd4 gives launch_wino4 a split-K workspace
- * (small grids then split the K loop over items + a reduce pass) unless frt_set_wino4_split(0). */
+ * (small grids then split the K loop over items + a reduce pass) unless frt_set_wino4_split(0).
+ * frt_conv2d_winograd4_ex's blk: W4_BLK_* bits (1 x, 2 res, 4 y): that tensor is channel-blocked [B][C/16][H][W][16] instead
+ * of NHWC; a residual laid out unlike y is for epi 2 only (launch_wino4 refuses epi 5: FR_ERR_HIP). */
 int frt_set_wino4_split(int on);
 /* A/B (process-wide): the ConvTile of the fused stride-2 conv2 + conv-shortcut launches of
  * non-serving batches (-1: the built-in rule).  Forwards already captured in graphs keep theirs. */
@@ -114,10 +116,20 @@ int frt_set_wino4_blocked(fr_handle* h, int on);
  * serving kernel are stored channel-blocked ([n][C/16][H][W][16]) instead of NHWC. */
 int frt_set_small_conv_blocked(fr_handle* h, int on);
 /* The serving-batch kernel alone: y = epi(conv3x3 pad 1 stride s (x) [+ conv1x1 stride s (x2)
- * against weight columns 9*cin .. + cin2]), w [cout][9*cin + cin2]; pre-BN only with epi 1;
+ * against weight columns 9*cin .. + cin2]), w [cout][9*cin + cin2]; pre-BN only with epi 1 (epi 1
+ * without it is the instance conv1 runs on a y2 input);
  * epi 0, 1, 2 (res shaped like y) or 3 (res [B][H][W][cout], read at (s oy, s ox)).
- * cin, cout, cin2 % 16 == 0.  Synchronises the stream before it returns (it frees the
- * temporary fragment-order copy of w it launched with). */
+ * blk: CONVS_BLK_* bits (1 x, 2 x2, 4 res, 8 y): that tensor is channel-blocked
+ * [B][C/16][H][W][16] instead of NHWC.  y2 (nullable): also y2 = y * y2_scale[c] + y2_shift[c], in
+ * y's shape and layout.  cin, cout, cin2 % 16 == 0.  What launch_convs refuses (pre-BN with another
+ * epilogue or more than 512 channels, cin2 > 256 or without x2, a missing epilogue operand, y2
+ * without its scale / shift) is FR_ERR_INVALID_ARGUMENT with y untouched.  Synchronises the stream
+ * before it returns (it frees the temporary fragment-order copy of w it launched with).
+ * frt_conv2d_small is frt_conv2d_small_ex with blk = 0 and no y2 (its callers' signature stays). */
+int frt_conv2d_small_ex(const float* x, const float* x2, const float* w, float* y, int B, int H, int W, int cin,
+                        int cin2, int cout, int stride, const float* pre_scale, const float* pre_shift,
+                        const float* post_scale, const float* post_shift, const float* prelu, const float* res, int epi,
+                        int blk, float* y2, const float* y2_scale, const float* y2_shift, void* stream);
 int frt_conv2d_small(const float* x, const float* x2, const float* w, float* y, int B, int H, int W, int cin,
                      int cin2, int cout, int stride, const float* pre_scale, const float* pre_shift,
                      const float* post_scale, const float* post_shift, const float* prelu, const float* res, int epi,
@@ -129,11 +141,24 @@ int frt_set_fuse_shortcut(fr_handle* h, int on);
 int frt_conv2d_winograd4(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout,
                          const float* pre_scale, const float* pre_shift, const float* post_scale,
                          const float* post_shift, const float* prelu, const float* res, int epi, void* stream);
+/* (frt_conv2d_winograd4 is this with blk = 0) */
+int frt_conv2d_winograd4_ex(const float* x, const float* w, float* y, int B, int H, int W, int cin, int cout,
+                            const float* pre_scale, const float* pre_shift, const float* post_scale,
+                            const float* post_shift, const float* prelu, const float* res, int epi, int blk,
+                            void* stream);
 
 /* Fused preprocess + input_layer on uint8 RGB [B][112][112][3]; w27x64 is the
  * repacked [ky][kx][c_rgb][64] weight; lut the 256-entry normalisation table. */
 int frt_stem(const uint8_t* img, int B, const float* lut, const float* w27x64, const float* bn_scale,
              const float* bn_shift, const float* prelu, float* y, void* stream);
+
+/* head_reduce_kernel alone: emb [n][512] = tail(sum over s < nsplit of partial[s * split_stride +
+ * row * 512 + c] + fc_bias[c]) * bn_scale[c] + bn_shift[c], then x / ||x|| with model_l2 and
+ * e / (||e|| + 1e-8) with normalize.  nsplit < 1, split_stride < n * 512, n < 1 or a null pointer
+ * is FR_ERR_INVALID_ARGUMENT before any launch.  Asynchronous on stream. */
+int frt_head_reduce(const float* partial, int nsplit, long long split_stride, const float* fc_bias,
+                    const float* bn_scale, const float* bn_shift, float* emb, int n, int normalize, int model_l2,
+                    void* stream);
 
 /* The host similarity fit of fr_align_faces: src/dst float [n][2] -> M double [2][3]. */
 int frt_fit_similarity(const float* src, const float* dst, int n, double* M);

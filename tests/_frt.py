@@ -20,8 +20,8 @@ def lib():
         L.frt_conv_split_fixup.argtypes = [_P, _I, ctypes.c_longlong] + [_I] * 4 + [_P] * 3 + [_I] * 3 + [_P, _P]
         L.frt_conv2d_winograd.restype = _I
         L.frt_conv2d_winograd.argtypes = [_P, _P, _P] + [_I] * 5 + [_P] * 6 + [_I, _P]
-        L.frt_conv2d_winograd4.restype = _I
-        L.frt_conv2d_winograd4.argtypes = [_P, _P, _P] + [_I] * 5 + [_P] * 6 + [_I, _P]
+        L.frt_conv2d_winograd4_ex.restype = _I
+        L.frt_conv2d_winograd4_ex.argtypes = [_P, _P, _P] + [_I] * 5 + [_P] * 6 + [_I, _I, _P]
         L.frt_set_wino4_split.restype = _I
         L.frt_set_wino4_split.argtypes = [_I]
         L.frt_set_conv2sc_tile.restype = _I
@@ -52,8 +52,10 @@ def lib():
         L.frt_set_small_conv_pixels.argtypes = [_P, _I]
         L.frt_set_wino4_blocked.restype = _I
         L.frt_set_wino4_blocked.argtypes = [_P, _I]
-        L.frt_conv2d_small.restype = _I
-        L.frt_conv2d_small.argtypes = [_P, _P, _P, _P] + [_I] * 7 + [_P] * 6 + [_I, _P]
+        L.frt_conv2d_small_ex.restype = _I
+        L.frt_conv2d_small_ex.argtypes = [_P, _P, _P, _P] + [_I] * 7 + [_P] * 6 + [_I, _I, _P, _P, _P, _P]
+        L.frt_head_reduce.restype = _I
+        L.frt_head_reduce.argtypes = [_P, _I, ctypes.c_longlong, _P, _P, _P, _P, _I, _I, _I, _P]
         L.frt_stem.restype = _I
         L.frt_stem.argtypes = [_P, _I, _P, _P, _P, _P, _P, _P, _P]
         L.frt_topk.restype = _I
@@ -128,17 +130,65 @@ def conv_split_fixup(part, S, stride, B, Ho, Wo, cout, post, res=None, res_hw=(0
     return y
 
 
-def conv2d_winograd(x, w, B, H, W, cin, cout, pre=None, post=None, prelu=None, res=None, epi=1, m=2):
+W4_BLK_X, W4_BLK_RES, W4_BLK_Y = 1, 2, 4
+CONVS_BLK_X, CONVS_BLK_X2, CONVS_BLK_RES, CONVS_BLK_Y = 1, 2, 4, 8
+
+
+def to_blocked(nhwc):
+    """[B][H][W][C] -> the channel-blocked [B][C/16][H][W][16] (contiguous)."""
+    B, H, W, C = nhwc.shape
+    return nhwc.view(B, H, W, C // 16, 16).permute(0, 3, 1, 2, 4).contiguous()
+
+
+def from_blocked(t):
+    """[B][C/16][H][W][16] -> NHWC [B][H][W][C] (contiguous)."""
+    B, CB, H, W, _ = t.shape
+    return t.permute(0, 2, 3, 1, 4).contiguous().view(B, H, W, CB * 16)
+
+
+def _as(t, blocked):
+    """A wrapper's NHWC input in the layout the launch reads it in."""
+    return t if t is None or not blocked else to_blocked(t)
+
+
+def _unblock(y, blocked):
+    """A wrapper's output buffer (allocated in the NHWC shape; the blocked layout has the same float
+    count, so every element of it is written too) back in NHWC."""
+    if not blocked:
+        return y
+    B, H, W, C = y.shape
+    return from_blocked(y.view(B, C // 16, H, W, 16))
+
+
+def conv2d_winograd(x, w, B, H, W, cin, cout, pre=None, post=None, prelu=None, res=None, epi=1, m=2, blk=0, out=None):
     """Winograd F(mxm,3x3) stride-1 conv (m = 2 or 4);
-    x NHWC cuda f32, w [cout][3][3][cin] cuda f32."""
-    y = torch.full((B, H, W, cout), float("nan"), device=x.device)
+    x NHWC cuda f32, w [cout][3][3][cin] cuda f32.  blk (m = 4): the W4_BLK_* tensors are handed to
+    the kernel channel-blocked (x and res are blocked here, y is unblocked here: NHWC in and out).
+    out: the caller's buffer instead of a fresh NaN-filled one (returned as the kernel left it)."""
+    y = torch.full((B, H, W, cout), float("nan"), device=x.device) if out is None else out
+    assert y.shape == (B, H, W, cout) and y.dtype == torch.float32 and y.is_contiguous()
     ps, ph = (pre if pre is not None else (None, None))
     qs, qh = post
-    fn = lib().frt_conv2d_winograd4 if m == 4 else lib().frt_conv2d_winograd
-    rc = fn(_p(x), _p(w), _p(y), B, H, W, cin, cout, _p(ps), _p(ph), _p(qs), _p(qh),
-            _p(prelu), _p(res), epi, torch.cuda.current_stream().cuda_stream)
+    x, res = _as(x, blk & W4_BLK_X), _as(res, blk & W4_BLK_RES)
+    if m == 4:
+        rc = lib().frt_conv2d_winograd4_ex(_p(x), _p(w), _p(y), B, H, W, cin, cout, _p(ps), _p(ph), _p(qs), _p(qh),
+                                           _p(prelu), _p(res), epi, blk, torch.cuda.current_stream().cuda_stream)
+    else:
+        assert blk == 0
+        rc = lib().frt_conv2d_winograd(_p(x), _p(w), _p(y), B, H, W, cin, cout, _p(ps), _p(ph), _p(qs), _p(qh),
+                                       _p(prelu), _p(res), epi, torch.cuda.current_stream().cuda_stream)
     _lib.check(rc)
-    return y
+    return y if out is not None else _unblock(y, blk & W4_BLK_Y)
+
+
+def head_reduce(partial, nsplit, split_stride, fc_bias, bn_scale, bn_shift, n, normalize, model_l2, out=None):
+    """head_reduce_kernel alone: partial cuda f32 holding nsplit slabs `split_stride` floats apart,
+    each [n][512] -> emb [n][512] (NaN-filled first, or the caller's `out`)."""
+    emb = torch.full((n, 512), float("nan"), device=fc_bias.device) if out is None else out
+    rc = lib().frt_head_reduce(_p(partial), nsplit, split_stride, _p(fc_bias), _p(bn_scale), _p(bn_shift), _p(emb), n,
+                               int(normalize), int(model_l2), torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc)
+    return emb
 
 
 def stem(img, lut, w27x64, sc, sh, al):
@@ -242,9 +292,10 @@ def set_detector_row_reduction(handle, on):
     _lib.check(lib().frt_set_detector_row_reduction(handle.h, int(on)), handle.h)
 
 
-def conv2d_s2band(x, w, B, H, W, post, res):
-    """The stage-1 stride-2 band conv: x, res NHWC [B,H,W,64] cuda f32, w [64][3][3][64]."""
-    y = torch.full((B, H // 2, W // 2, 64), float("nan"), device=x.device)
+def conv2d_s2band(x, w, B, H, W, post, res, out=None):
+    """The stage-1 stride-2 band conv: x, res NHWC [B,H,W,64] cuda f32, w [64][3][3][64].
+    out: the caller's buffer instead of a fresh NaN-filled one (a test of a refusal)."""
+    y = torch.full((B, H // 2, W // 2, 64), float("nan"), device=x.device) if out is None else out
     rc = lib().frt_conv2d_s2band(_p(x), _p(w), _p(y), B, H, W, _p(post[0]), _p(post[1]), _p(res),
                                  torch.cuda.current_stream().cuda_stream)
     _lib.check(rc)
@@ -252,13 +303,25 @@ def conv2d_s2band(x, w, B, H, W, post, res):
 
 
 def conv2d_small(x, w, B, H, W, cin, cout, stride=1, x2=None, cin2=0, pre=None, post=None, prelu=None, res=None,
-                 epi=0):
-    """conv_small.hip's serving kernel: x NHWC cuda f32, w [cout][9*cin + cin2] cuda f32."""
+                 epi=0, blk=0, y2=None, out=None):
+    """conv_small.hip's serving kernel: x NHWC cuda f32, w [cout][9*cin + cin2] cuda f32.
+    blk: the CONVS_BLK_* tensors are handed to the kernel channel-blocked (x, x2 and res are blocked
+    here, y and y2 unblocked here: NHWC in and out).  y2: None, or (scale, shift) of the second
+    output, either of which may be None (a refusal); the call then returns (y, y2).
+    out: the caller's y buffer instead of a fresh NaN-filled one (returned as the kernel left it)."""
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    y = torch.full((B, Ho, Wo, cout), float("nan"), device=x.device)
+    y = torch.full((B, Ho, Wo, cout), float("nan"), device=w.device) if out is None else out
+    assert y.shape == (B, Ho, Wo, cout) and y.dtype == torch.float32 and y.is_contiguous()
     ps, ph = (pre if pre is not None else (None, None))
     qs, qh = post
-    rc = lib().frt_conv2d_small(_p(x), _p(x2), _p(w), _p(y), B, H, W, cin, cin2, cout, stride, _p(ps), _p(ph),
-                                _p(qs), _p(qh), _p(prelu), _p(res), epi, torch.cuda.current_stream().cuda_stream)
+    x, x2, res = _as(x, blk & CONVS_BLK_X), _as(x2, blk & CONVS_BLK_X2), _as(res, blk & CONVS_BLK_RES)
+    y2b, (s2, t2) = None, (None, None)
+    if y2 is not None:
+        y2b, (s2, t2) = torch.full_like(y, float("nan")), y2
+    rc = lib().frt_conv2d_small_ex(_p(x), _p(x2), _p(w), _p(y), B, H, W, cin, cin2, cout, stride, _p(ps), _p(ph),
+                                   _p(qs), _p(qh), _p(prelu), _p(res), epi, blk, _p(y2b), _p(s2), _p(t2),
+                                   torch.cuda.current_stream().cuda_stream)
     _lib.check(rc)
-    return y
+    if out is None:
+        y = _unblock(y, blk & CONVS_BLK_Y)
+    return y if y2 is None else (y, _unblock(y2b, blk & CONVS_BLK_Y))

@@ -298,6 +298,7 @@ def test_small_batch_match_vs_reference(handle, G):
     handle.gallery_set(torch.from_numpy(E).cuda())
     Q = g.standard_normal((17, 512)).astype(np.float32)
     Q[2] = E[min(1, G - 1)] * 3.0        # exact-tie query (G >= 7): rows 1 and G // 2 score the same
+    Q[4] = 0.0                           # 0 / (0 + 1e-8) = 0: every score exactly 0, one tie over the whole gallery
     for n in (1, 5, 16, 17):
         k = min(8 if n <= 16 else 5, G)
         q = torch.from_numpy(Q[:n]).cuda()
@@ -319,4 +320,7 @@ def test_small_batch_match_vs_reference(handle, G):
                     assert np.array_equal(got[r], order[r]), (n, r)
             if n >= 3 and G >= 7:
                 assert set(got[2][:2].tolist()) == {1, G // 2} and got[2][0] == max(1, G // 2)
+            if n >= 5:  # the all-zero query: scores exactly 0, the highest rows first (the tie policy)
+                assert np.all(sc.cpu().numpy()[4] == 0.0)
+                assert np.array_equal(got[4], np.arange(G - 1, G - 1 - k, -1)), (n, got[4])
     handle.gallery_set(torch.empty((0, 512), device="cuda"))

@@ -7,6 +7,8 @@ out (B^T, A^T entries) before the cancellations, so each output carries ~10x the
 The transforms add a few f32 roundings per output (input: 2 adds, output: 4 adds, filter: rounded
 once from double), well inside that bar; the network-level check compares whole embeddings.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -231,3 +233,85 @@ def test_network_winograd_vs_direct_vs_oracle(arch):
         s = p @ g.T
         assert np.abs(s - ref_s).max() <= 1e-4, algo
         assert np.array_equal(np.argsort(-s, axis=1, kind="stable")[:, :5], ref_top), algo
+
+
+@functools.lru_cache(maxsize=4)
+def _w4_layout_inputs(B, H, W, cin, cout, epi, seed):
+    """The f32 tensors of one F(4x4) launch (CPU; activations NHWC) and its float64 reference from
+    them, computed once for the layouts and schedules that share them and never changed."""
+    x = _rand(B, cin, H, W, seed=seed)
+    w = _rand(cout, cin, 3, 3, seed=seed + 1) / (cin * 9) ** 0.5
+    pre = (_rand(cin, seed=seed + 2, lo=0.5, hi=1.5), _rand(cin, seed=seed + 3, lo=-0.2, hi=0.2))
+    post = (_rand(cout, seed=seed + 4, lo=0.5, hi=1.5), _rand(cout, seed=seed + 5, lo=-0.2, hi=0.2))
+    al = _rand(cout, seed=seed + 6, lo=0.1, hi=0.4)
+    r = _rand(B, cout, H, W, seed=seed + 7)
+
+    def c(v):
+        return v.double().view(1, -1, 1, 1)
+    xin = x.double() * c(pre[0]) + c(pre[1]) if epi == 1 else x.double()
+    ref = F.conv2d(xin, w.double(), padding=1) * c(post[0]) + c(post[1])
+    ref = torch.where(ref > 0, ref, ref * c(al)) if epi == 1 else ref + r.double()
+    return _nhwc(x), w.permute(0, 2, 3, 1).contiguous(), pre, post, al, _nhwc(r), _nhwc(ref)
+
+
+W4_SHAPES = [
+    (2, 8, 12, 32, 64),     # 4 | H and W: no separators, 2 K-steps
+    (3, 7, 5, 48, 128),     # separators both ways, 3 K-steps, two cout blocks
+    (5, 14, 14, 64, 128),   # four images per canvas row, ragged last canvas row
+    (1, 1, 1, 16, 16),      # one pixel, one K-step (never split)
+]
+
+
+@pytest.mark.parametrize("epi", [1, 2])
+@pytest.mark.parametrize("B,H,W,cin,cout", W4_SHAPES)
+def test_winograd4_blocked_layouts(B, H, W, cin, cout, epi):
+    """Wino4Params::blk at the kernel: conv1 (pre-BN, epi 1) with x, y and both channel-blocked, conv2
+    (epi 2) with every combination of x, res and y -- the four with res and y in different layouts are
+    the RMIX 1 / 2 instances of a whole-item launch -- under the split-K schedule (the fixup's own
+    at(blk) addressing) and the whole-item one.  Against float64 at the file's F(4x4) bar, and
+    bitwise the NHWC launch of the same schedule: a layout moves addresses, not arithmetic.  The maps
+    are not square, so H * W * 16 cannot be confused with W * W * 16 or H * H * 16."""
+    x, w, pre, post, al, r, ref = _w4_layout_inputs(B, H, W, cin, cout, epi, 1900 + H + cin + epi)
+    xd, wd, rd = x.to(DEV), w.to(DEV), r.to(DEV)
+    kw = dict(post=(post[0].to(DEV), post[1].to(DEV)), epi=epi, m=4)
+    if epi == 1:
+        kw.update(pre=(pre[0].to(DEV), pre[1].to(DEV)), prelu=al.to(DEV))
+        layouts = [_frt.W4_BLK_X, _frt.W4_BLK_Y, _frt.W4_BLK_X | _frt.W4_BLK_Y]
+    else:
+        kw.update(res=rd)
+        layouts = list(range(1, 8))
+    L = _frt.lib()
+    try:
+        for split in (1, 0):
+            L.frt_set_wino4_split(split)
+            base = _frt.conv2d_winograd(xd, wd, B, H, W, cin, cout, **kw).cpu()
+            _close(base, ref, rel=REL[4])
+            for blk in layouts:
+                got = _frt.conv2d_winograd(xd, wd, B, H, W, cin, cout, blk=blk, **kw).cpu()
+                assert torch.isfinite(got).all(), f"split {split} blk {blk}: an output element was not written"
+                _close(got, ref, rel=REL[4])
+                assert torch.equal(got, base), f"split {split} blk {blk}: not bitwise the NHWC launch"
+    finally:
+        L.frt_set_wino4_split(1)
+
+
+@pytest.mark.parametrize("split", [1, 0])
+def test_winograd4_refuses_mixed_residual_layouts_it_has_no_instance_for(split):
+    """A residual laid out unlike y exists for epi 2 without pre-BN only: epi 5, or pre-BN, with
+    RES != Y is an error and nothing is written."""
+    B, H, W, cin, cout = 2, 8, 12, 32, 64
+    x, w, pre, post, al, r, _ = _w4_layout_inputs(B, H, W, cin, cout, 2, 1990)
+    xd, wd, rd = x.to(DEV), w.to(DEV), r.to(DEV)
+    post, pre = (post[0].to(DEV), post[1].to(DEV)), (pre[0].to(DEV), pre[1].to(DEV))
+    L = _frt.lib()
+    try:
+        L.frt_set_wino4_split(split)
+        for blk in (_frt.W4_BLK_RES, _frt.W4_BLK_Y, _frt.W4_BLK_X | _frt.W4_BLK_RES):
+            for kw in (dict(epi=5, prelu=al.to(DEV)), dict(epi=2, pre=pre)):
+                out = torch.full((B, H, W, cout), float("nan"), device=DEV)
+                with pytest.raises((ValueError, RuntimeError)):
+                    _frt.conv2d_winograd(xd, wd, B, H, W, cin, cout, post=post, res=rd, m=4, blk=blk, out=out, **kw)
+                torch.cuda.synchronize()
+                assert torch.isnan(out).all(), "a refused launch wrote to y"
+    finally:
+        L.frt_set_wino4_split(1)
