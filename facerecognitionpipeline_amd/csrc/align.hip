@@ -211,11 +211,11 @@ __global__ __launch_bounds__(256) void blur_kernel(const uint8_t* __restrict__ c
   extern __shared__ __align__(8) uint8_t s_dyn[];
   const int n = H * W;
   const int nch = (n + NP_BUFSIZE - 1) / NP_BUFSIZE;
-  double* val = reinterpret_cast<double*>(s_dyn);   // [2][nch * 128]: two adjacent levels' values
+  long long* red = reinterpret_cast<long long*>(s_dyn);  // [4]: block_sum_i64's wave sums
+  double* val = reinterpret_cast<double*>(red + 4);      // [2][nch * 128]: two adjacent levels' values
   int* lo = reinterpret_cast<int*>(val + 2 * nch * NP_SLOTS);  // [nch * 255]: node starts
   int* len = lo + nch * NP_NODES;                               // [nch * 255]: node lengths
   uint8_t* s_gray = reinterpret_cast<uint8_t*>(len + nch * NP_NODES);
-  __shared__ long long red[4];
   const int tid = threadIdx.x;
   const BlurImg im{crops + (long long)blockIdx.x * n * C, H, W, C};
   for (int i = tid; i < n; i += 256) s_gray[i] = (uint8_t)im.gray(i);
@@ -293,10 +293,12 @@ __global__ __launch_bounds__(256) void blur_final_kernel(const double* __restric
   var[img] = acc / (double)npix;
 }
 
-// dynamic LDS of blur_kernel: two levels of values, the trees' node ranges, the gray image
+// All the LDS of blur_kernel, which declares none statically (so this figure against BLUR_LDS_MAX
+// is the whole decision): the int64 wave sums, two levels of values, the trees' node ranges, the
+// gray image
 size_t blur_lds_bytes(int H, int W) {
   const size_t n = (size_t)H * W, nch = (n + NP_BUFSIZE - 1) / NP_BUFSIZE;
-  return 2 * nch * NP_SLOTS * 8 + 2 * nch * NP_NODES * 4 + n;
+  return 4 * sizeof(long long) + 2 * nch * NP_SLOTS * 8 + 2 * nch * NP_NODES * 4 + n;
 }
 
 size_t blur_workspace_bytes(int n, int H, int W) {

@@ -270,6 +270,8 @@ hipError_t launch_fit_similarity(const FitSlots& p, hipStream_t s);
 // (C = 3 / 4: RGB(A) -> gray; C = 1: gray) -> var[n] (double).  Images whose gray copy and
 // summation trees fit BLUR_LDS_MAX bytes of LDS take one block each; larger ones take three
 // launches over (chunk, image) blocks and blur_workspace_bytes(n, H, W) of device workspace ws.
+// BLUR_LDS_MAX is a gfx950 workgroup's whole LDS and blur_lds_bytes all that blur_kernel uses (it
+// has no static LDS): at most 106,576 pixels take the one-block form.
 constexpr size_t BLUR_LDS_MAX = 160 * 1024;
 size_t blur_lds_bytes(int H, int W);
 size_t blur_workspace_bytes(int n, int H, int W);

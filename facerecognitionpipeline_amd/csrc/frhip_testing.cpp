@@ -525,11 +525,16 @@ int frt_detector_postprocess(fr_handle* h, const float* heads, int n, float det_
                               (hipStream_t)stream);
 }
 
-int frt_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, void* stream) {
+int frt_topk_ex(const float* scores, int n, int G, int k, int low_index_first, int32_t* idx, float* val,
+                void* stream) {
   if (k < 1 || k > G) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_topk: k must be in [1, G]");
-  hipError_t e = launch_topk(scores, n, G, k, idx, val, (hipStream_t)stream);
+  hipError_t e = launch_topk(scores, n, G, k, idx, val, (hipStream_t)stream, low_index_first != 0);
   if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_topk: ") + hipGetErrorString(e));
   return FR_OK;
+}
+
+int frt_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, void* stream) {
+  return frt_topk_ex(scores, n, G, k, 0, idx, val, stream);
 }
 
 }  // extern "C"

@@ -189,6 +189,11 @@ int frt_det_stem(const uint8_t* img, int B, int H, int W, int C, const float* w2
 
 /* Row-wise top-k of a [n][G] score matrix (score desc, equal scores by descending index; k in [1, G]). */
 int frt_topk(const float* scores, int n, int G, int k, int32_t* idx, float* val, void* stream);
+/* The same with the tie order chosen: low_index_first != 0 ranks equal scores by ASCENDING index
+ * (the instances fr_match_identities launches), 0 is frt_topk.  NaN never ranks; a row with fewer
+ * than k rankable scores ends in idx -1 / val -inf.  scores needs 4-byte alignment only. */
+int frt_topk_ex(const float* scores, int n, int G, int k, int low_index_first, int32_t* idx, float* val,
+                void* stream);
 
 /* Process-wide: fr_identity_scores scores at most `probes` probes per GEMM chunk (0: the built-in
  * rule, the most whose [probes][G] score matrix stays below 2 GiB), so a test can put a chunk seam

@@ -60,6 +60,8 @@ def lib():
         L.frt_stem.argtypes = [_P, _I, _P, _P, _P, _P, _P, _P, _P]
         L.frt_topk.restype = _I
         L.frt_topk.argtypes = [_P, _I, _I, _I, _P, _P, _P]
+        L.frt_topk_ex.restype = _I
+        L.frt_topk_ex.argtypes = [_P, _I, _I, _I, _I, _P, _P, _P]
         L.frt_detector_forward.restype = _I
         L.frt_detector_forward.argtypes = [_P, _P, _I, _I, _I, _P, _P, _P]
         L.frt_set_detector_row_reduction.restype = _I
@@ -264,11 +266,19 @@ def detector_postprocess(handle, heads, det_scale=1.0, det_scales=None, det_thre
     return dets, counts
 
 
-def topk(scores, k):
+def topk(scores, k, low_first=False):
+    """Row-wise top-k of scores f32 [n][G], read at the tensor's own data pointer (a row-contiguous
+    view that starts inside its buffer is taken as it is).  low_first: equal scores by ascending
+    index (fr_match_identities' order) instead of descending.  Outputs pre-filled (idx -2, val NaN)."""
     n, G = scores.shape
-    idx = torch.empty((n, k), dtype=torch.int32, device=scores.device)
-    val = torch.empty((n, k), dtype=torch.float32, device=scores.device)
-    _lib.check(lib().frt_topk(_p(scores), n, G, k, _p(idx), _p(val), torch.cuda.current_stream().cuda_stream))
+    assert scores.dtype == torch.float32 and scores.is_contiguous()
+    idx = torch.full((n, k), -2, dtype=torch.int32, device=scores.device)
+    val = torch.full((n, k), float("nan"), dtype=torch.float32, device=scores.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    if low_first:
+        _lib.check(lib().frt_topk_ex(_p(scores), n, G, k, 1, _p(idx), _p(val), stream))
+    else:
+        _lib.check(lib().frt_topk(_p(scores), n, G, k, _p(idx), _p(val), stream))
     return idx, val
 
 

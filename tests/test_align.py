@@ -9,6 +9,7 @@ RANSAC consensus drops outliers, cv::RNG's sequence and the adaptive iteration
 count follow OpenCV's published formulas).
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -197,7 +198,8 @@ def test_blur_kernel_matches_restatement():
     big = rng.integers(0, 256, (2, 224, 224, 3), dtype=np.uint8)
     assert _blur_equal(qf.compute_blur_scores(big), [A.blur_score(c) for c in big])
     # smooth crops (small variances, many equal Laplacians) and odd sizes: chunk and leaf edges;
-    # up to 256 one block per image, beyond (320, 448: 13 / 25 chunks) the multi-block form
+    # up to 320 (13 chunks, 155,576 bytes of LDS) one block per image, 448 (25 chunks) the
+    # multi-block form; the limit between the two forms: test_blur_at_the_one_block_limit
     for S in (7, 8, 9, 90, 91, 129, 200, 256, 320, 448):
         yy, xx = np.mgrid[0:S, 0:S]
         sm = np.stack([(yy * 3 + xx) % 256, (xx * 2) % 256, (yy + 40) % 256], -1).astype(np.uint8)[None]
@@ -235,6 +237,70 @@ def test_blur_any_shape_gray_and_rgba():
     assert qf.compute_blur_scores(np.zeros((0, 8, 8, 3), np.uint8)).shape == (0,)
     with pytest.raises(ValueError):
         qf.compute_blur_scores(np.zeros((8, 8), np.uint8))
+
+
+# blur_kernel (one block per image) keeps everything in LDS: 32 bytes of int64 wave sums, per chunk of
+# 8192 pixels 2 * 128 float64 values and 2 * 255 int32 node ranges (4088 bytes), and one gray byte per
+# pixel: 32 + 4088 * ceil(n / 8192) + n bytes for n pixels, all of it dynamic.  A gfx950 workgroup has
+# 160 KiB = 163,840 bytes.  13 chunks (n <= 106,496) need at most 159,672; with 14 chunks
+# 32 + 57,232 + n <= 163,840 holds up to n = 106,576.  So 106,576 pixels is the largest one-block
+# image and 106,577 the smallest that takes the three-launch form.  (Before the wave sums were counted
+# the launcher drew the line at 106,608 and asked for up to 163,872 bytes in between.)
+ONE_BLOCK_MAX_PIXELS = 106_576
+BLUR_SEAM_SHAPES = [
+    (256, 416),    # 106,496: 13 full chunks
+    (16, 6661),    # 106,576: the last one-block count
+    (197, 541),    # 106,577: the first multi-block count
+    (323, 330),    # 106,590  \
+    (325, 328),    # 106,600   > counts the launcher once sent to one block with too much LDS
+    (17, 6271),    # 106,607  /
+    (48, 2221),    # 106,608: the last of them
+    (181, 589),    # 106,609: multi-block before and after
+]
+
+
+@functools.lru_cache(maxsize=None)
+def _blur_seam_case(H, W):
+    """Two RGBA images of H x W, one smooth and one random, and the reference scores of their RGB and
+    gray forms (computed once for the three channel counts; the arrays are never changed)."""
+    rng = np.random.default_rng(H * 10007 + W)
+    yy, xx = np.mgrid[0:H, 0:W]
+    smooth = np.stack([(yy * 3 + xx) % 256, (xx * 2) % 256, (yy + 40) % 256, (xx + yy) % 256], -1).astype(np.uint8)
+    rgba = np.stack([smooth, rng.integers(0, 256, (H, W, 4), dtype=np.uint8)])
+    gray = np.ascontiguousarray(rgba[..., 1])
+    ref_rgb = np.array([A.blur_score(c[..., :3]) for c in rgba])
+    ref_gray = np.array([A.laplacian_var(g) for g in gray])
+    for a in (rgba, gray, ref_rgb, ref_gray):
+        a.setflags(write=False)
+    return rgba, gray, ref_rgb, ref_gray
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("C", [1, 3, 4])
+@pytest.mark.parametrize("H,W", BLUR_SEAM_SHAPES)
+def test_blur_across_the_one_block_limit(H, W, C):
+    """Pixel counts around the largest image blur_kernel's LDS holds, gray, RGB and RGBA: whichever
+    form the launcher picks returns numpy's bits, and never asks for more LDS than a workgroup has."""
+    from facerecognitionpipeline_amd.face_recognition import FaceQualityFilter
+    rgba, gray, ref_rgb, ref_gray = _blur_seam_case(H, W)
+    qf = FaceQualityFilter()
+    if C == 1:
+        assert _blur_equal(qf.compute_blur_scores(gray.copy()), ref_gray)
+    else:
+        assert _blur_equal(qf.compute_blur_scores(rgba[..., :C].copy()), ref_rgb)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W,over", [(4, 26644, 0), (541, 197, 1)], ids=["last_one_block", "first_multi_block"])
+def test_blur_at_the_one_block_limit(H, W, over):
+    """One image on each side of ONE_BLOCK_MAX_PIXELS, in other shapes than the table's (long rows;
+    tall and narrow), a batch of 3 so the multi-block form's per-image workspace slices matter."""
+    from facerecognitionpipeline_amd.face_recognition import FaceQualityFilter
+    assert H * W == ONE_BLOCK_MAX_PIXELS + over
+    rng = np.random.default_rng(H)
+    rgb = rng.integers(0, 256, (3, H, W, 3), dtype=np.uint8)
+    rgb[1] = rgb[1] // 32 * 32
+    assert _blur_equal(FaceQualityFilter().compute_blur_scores(rgb), [A.blur_score(c) for c in rgb])
 
 
 @pytest.mark.gpu
