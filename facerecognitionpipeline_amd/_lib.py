@@ -69,6 +69,7 @@ _SIGNATURES = {
     "fr_detect_device": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P]),
     "fr_align_device": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "fr_blur_scores_device": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "fr_quality_gate_device": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fr_set_precision": (_I, [_P, _I]),
     "fr_set_conv_algorithm": (_I, [_P, _I]),
     "fr_set_graph_batch": (_I, [_P, _I]),
@@ -83,6 +84,16 @@ _SIGNATURES = {
     "fr_last_error": (ctypes.c_char_p, [_P]),
     "fr_version": (ctypes.c_char_p, []),
 }
+
+
+
+class GateConfig(ctypes.Structure):
+    """fr_gate_config."""
+    _fields_ = [(k, ctypes.c_double) for k in ("min_det_score", "min_face_size", "max_yaw", "max_pitch", "max_roll",
+                                               "blur_threshold")] + [("check_blur", ctypes.c_int)]
+
+
+GATE_OUTPUTS = ("stage", "metrics", "bbox", "rank", "rows", "frame_offsets", "valid_slots", "n_valid")
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()
@@ -667,6 +678,37 @@ class Handle:
         check(self._lib.fr_blur_scores_device(self.h, ptr(crops), n, crops.shape[1], crops.shape[2], c, ptr(out),
                                               stream_of(self.device)), self.h)
         return out
+
+    def quality_gate_device(self, dets: torch.Tensor, counts, ok, blur, config, out=None):
+        """The quality gate, the per-frame order and the packed face lists on the device, no
+        synchronisation (fr_quality_gate_device).  dets float32 [n,F,15]; counts int32 [n] or None;
+        ok uint8 [n,F] or None; blur float64 with n * F elements or None; ``config``: the seven
+        fields of fr_gate_config by name -> a dict of the device tensors ``GATE_OUTPUTS``: stage uint8
+        [n,F], metrics f64 [n,F,5], bbox int32 [n,F,4], rank int32 [n,F], rows int32 [n*F],
+        frame_offsets int32 [n+1], valid_slots int32 [n*F], n_valid int32 [1].  ``out``: such a dict
+        to write again (for graph capture)."""
+        if (not isinstance(dets, torch.Tensor) or dets.dtype != torch.float32 or dets.dim() != 3
+                or dets.shape[2] != 15):
+            raise ValueError("dets must be float32 [n,F,15] detection rows")
+        self._require_device("dets", dets)
+        dets = dets.contiguous()
+        n, F = dets.shape[0], dets.shape[1]
+        for name, t, dtype, numel in (("counts", counts, torch.int32, n), ("ok", ok, torch.uint8, n * F),
+                                      ("blur", blur, torch.float64, n * F)):
+            if t is not None:
+                if t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
+                    raise ValueError(f"{name} must be a contiguous {dtype} tensor of {numel} elements")
+                self._require_device(name, t)
+        shapes = {"stage": ((n, F), torch.uint8), "metrics": ((n, F, 5), torch.float64),
+                  "bbox": ((n, F, 4), torch.int32), "rank": ((n, F), torch.int32), "rows": ((n * F,), torch.int32),
+                  "frame_offsets": ((n + 1,), torch.int32), "valid_slots": ((n * F,), torch.int32),
+                  "n_valid": ((1,), torch.int32)}
+        o = {k: self._out(k, None if out is None else out.get(k), *shapes[k], zero=(n == 0)) for k in GATE_OUTPUTS}
+        cfg = GateConfig(**{k: config[k] for k, _ in GateConfig._fields_})
+        check(self._lib.fr_quality_gate_device(self.h, ptr(dets), ptr(counts), ptr(ok), ptr(blur), n, F,
+                                               ctypes.byref(cfg), *(ptr(o[k]) for k in GATE_OUTPUTS),
+                                               stream_of(self.device)), self.h)
+        return o
 
     def _image_list(self, images):
         """A list of uint8 [H,W,3] device tensors -> (contiguous tensors on the handle's device, host

@@ -23,7 +23,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = "gfx950"
 SOURCES = ["conv_winograd4.hip", "conv_winograd.hip", "conv_s2.hip", "conv_small.hip","conv_f32_w4.hip", "conv_f32_w8.hip", "conv_bf16x3.hip", "conv_det.hip", "conv_mfma.hip",
-           "embed_misc.hip", "align.hip", "align_fit.hip", "augment.hip", "gallery.hip", "track.hip", "rollcall.hip", "capture.hip", "live.hip", "server.hip", "evaluate.hip", "identify.hip", "detect.hip", "frhip_runtime.cpp", "batch_ops.cpp", "finalize.cpp",
+           "embed_misc.hip", "align.hip", "align_fit.hip", "gate.hip", "augment.hip", "gallery.hip", "track.hip", "rollcall.hip", "capture.hip", "live.hip", "server.hip", "evaluate.hip", "identify.hip", "detect.hip", "frhip_runtime.cpp", "batch_ops.cpp", "finalize.cpp",
            "conv_dispatch.cpp", "embed_forward.cpp", "align_host.cpp", "frhip_testing.cpp", "detector.cpp"]
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(REPO, "include"), "-I" + CSRC]

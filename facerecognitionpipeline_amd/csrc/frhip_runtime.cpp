@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "gate_math.h"
 #include "runtime.h"
 
 using namespace frhip;
@@ -556,6 +557,45 @@ int fr_blur_scores_device(fr_handle* h, const uint8_t* crops, int n, int height,
   if (n == 0) return FR_OK;
   DeviceGuard dg(h->device);
   return blur_device(h, crops, n, height, width, channels, scores, (hipStream_t)stream);
+}
+
+int fr_quality_gate_device(fr_handle* h, const float* dets, const int32_t* counts, const uint8_t* ok,
+                           const double* blur, int n_frames, int max_faces, const fr_gate_config* cfg,
+                           uint8_t* stage, double* metrics, int32_t* bbox, int32_t* rank, int32_t* rows,
+                           int32_t* frame_offsets, int32_t* valid_slots, int32_t* n_valid, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (n_frames < 0 || max_faces < 1 || max_faces > FR_GATE_MAX_FACES ||
+      (long long)n_frames * max_faces >= (1ll << 31) || !cfg)
+    return fail(h, FR_ERR_INVALID_ARGUMENT,
+                "bad quality gate arguments (n_frames >= 0, max_faces in [1, " + std::to_string(FR_GATE_MAX_FACES) +
+                    "], a config)");
+  GateArgs a{};
+  if (!gate_limits(*cfg, blur != nullptr, &a.lim))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "a quality gate limit is not finite or lies beyond +-FLT_MAX");
+  if (n_frames == 0) return FR_OK;
+  if (!dets || !stage || !metrics || !bbox || !rank || !rows || !frame_offsets || !valid_slots || !n_valid)
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "NULL quality gate buffer (only counts, ok and blur may be NULL)");
+  DeviceGuard dg(h->device);
+  if (int rc = ensure_buf(h, &h->gate_ws, &h->gate_ws_cap, (size_t)n_frames * sizeof(int32_t))) return rc;
+  a.dets = dets;
+  a.counts = counts;
+  a.ok = ok;
+  a.blur = blur;
+  a.n_frames = n_frames;
+  a.F = max_faces;
+  a.stage = stage;
+  a.metrics = metrics;
+  a.bbox = bbox;
+  a.rank = rank;
+  a.rows = rows;
+  a.frame_offsets = frame_offsets;
+  a.valid_slots = valid_slots;
+  a.n_valid = n_valid;
+  a.frame_valid = static_cast<int32_t*>(h->gate_ws);
+  const hipError_t e = launch_quality_gate(a, (hipStream_t)stream);
+  if (e != hipSuccess) return launch_fail(h, "quality gate", e);
+  return FR_OK;
 }
 
 int fr_set_precision(fr_handle* h, int mode) {

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "gate_math.h"
 #include "runtime.h"
 // (after runtime.h: it declares fr_handle through frhip.h)
 #include "../../include/frhip_testing.h"
@@ -434,6 +435,60 @@ int frt_fit_similarity_device(const float* landmarks, int n, int out_size, doubl
   (void)hipFree(buf);
   if (e != hipSuccess)
     return fail(nullptr, FR_ERR_HIP, std::string("frt_fit_similarity_device: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_quality_gate_host(const float* dets, const int32_t* counts, const uint8_t* ok, const double* blur,
+                          int n_frames, int max_faces, const fr_gate_config* cfg, uint8_t* stage, double* metrics,
+                          int32_t* bbox, int32_t* rank, int32_t* rows, int32_t* frame_offsets, int32_t* valid_slots,
+                          int32_t* n_valid) {
+  const int F = max_faces;
+  if (n_frames < 0 || F < 1 || F > FR_GATE_MAX_FACES || (long long)n_frames * F >= (1ll << 31) || !cfg)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_quality_gate_host: bad n_frames / max_faces / config");
+  GateLimits lim;
+  if (!gate_limits(*cfg, blur != nullptr, &lim))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_quality_gate_host: a limit is not finite or beyond +-FLT_MAX");
+  if (n_frames == 0) return FR_OK;
+  if (!dets || !stage || !metrics || !bbox || !rank || !rows || !frame_offsets || !valid_slots || !n_valid)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_quality_gate_host: NULL buffer");
+  std::vector<double> key((size_t)F);
+  int total = 0, n_ok = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    const int live = gate_live(counts, f, F);
+    const size_t base = (size_t)f * F;
+    for (int i = 0; i < F; ++i) {
+      const size_t slot = base + i;
+      GateSlot r{};
+      if (i < live) {
+        r = gate_slot(dets + slot * 15, ok ? ok[slot] : 1, lim.check_blur ? blur[slot] : 0.0, lim);
+        key[i] = r.key;
+      } else {
+        r.stage = FR_GATE_NOT_LIVE;
+        rank[slot] = -1;
+      }
+      stage[slot] = (uint8_t)r.stage;
+      const double m[5] = {r.det_score, r.blur_score, r.yaw, r.pitch, r.roll};
+      std::copy(m, m + 5, metrics + slot * 5);
+      const int32_t b[4] = {r.x0, r.y0, r.x1, r.y1};
+      std::copy(b, b + 4, bbox + slot * 4);
+    }
+    frame_offsets[f] = total;
+    for (int i = 0; i < live; ++i) {
+      int before = 0;
+      for (int j = 0; j < live; ++j) before += gate_before(key[j], j, key[i], i);
+      rank[base + i] = before;
+      rows[total + before] = (int32_t)(base + i);
+    }
+    for (int r = 0; r < live; ++r) {  // rows of this frame are complete: the valid ones in rows order
+      const int32_t slot = rows[total + r];
+      if (stage[slot] == FR_GATE_VALID) valid_slots[n_ok++] = slot;
+    }
+    total += live;
+  }
+  frame_offsets[n_frames] = total;
+  n_valid[0] = n_ok;
+  std::fill(rows + total, rows + (size_t)n_frames * F, -1);
+  std::fill(valid_slots + n_ok, valid_slots + (size_t)n_frames * F, -1);
   return FR_OK;
 }
 

@@ -226,6 +226,9 @@ struct fr_handle {
   // asynchronous, and a captured graph keeps replaying into it)
   void* align_slots = nullptr;
   size_t align_slots_cap = 0;
+  // fr_quality_gate_device: [n_frames] int32 valid slots per frame, between its two launches
+  void* gate_ws = nullptr;
+  size_t gate_ws_cap = 0;
 
   int cus = 0;  // CUs of the device (ensure_stream_k)
   bool stream_k = true;
@@ -339,6 +342,7 @@ struct fr_handle {
     (void)hipFree(blur_out);
     (void)hipFree(blur_ws);
     (void)hipFree(align_slots);
+    (void)hipFree(gate_ws);
     if (dev_err) (void)hipHostFree(dev_err);
   }
 };

@@ -384,10 +384,14 @@ class CameraFaceCapture:
                                                    "blur_threshold": 100})
 
     def __init__(self, output_dir="output/camera_captures", skip_frames=5, target_frames_per_person=12,
-                 min_quality_score=0.5, processor=None, device=None, verbose: bool = True):
+                 min_quality_score=0.5, processor=None, device=None, verbose: bool = True,
+                 device_chain: bool = False):
         import torch
         from .face_recognition import FaceProcessor
         self.skip_frames = skip_frames
+        # True: a clip's sampled frames go through detect, align, blur and the quality gate on the
+        # device in one pass (face_recognition.device_chain) instead of per-frame calls and a host gate
+        self.device_chain = bool(device_chain)
         self.frame_count = 0
         self.verbose = verbose
         self.processor = processor if processor is not None else FaceProcessor(device=device,
@@ -405,7 +409,14 @@ class CameraFaceCapture:
         """Per sampled frame the reference's ``process_numpy(frame, return_all=True)`` list (its
         order: descending det_score x blur_score), with the aligned crops left on the device:
         ``(frame numbers, [[face dict, ...], ...], crops uint8 [total,S,S,3] on the device)`` where
-        a face dict carries ``'crop_row'`` instead of ``'aligned_face'``."""
+        a face dict carries ``'crop_row'`` instead of ``'aligned_face'``.
+
+        With ``device_chain`` the sampled frames run detect_device -> align_device ->
+        blur_scores_device -> gate_device in one pass with one copy to the host, the order comes from
+        the gate's ranks, ``crops`` holds one crop per slot ([frames * max_faces,S,S,3]) and
+        ``'crop_row'`` is the slot index.  The same faces, order and flags; yaw and roll as
+        ``quality_gate_host`` states them (within 1e-4 degrees of the host gate's).  A detection whose
+        similarity fit fails, where the host chain raises, is ``is_valid: False`` there."""
         import torch
         p = self.processor
         if isinstance(frames, torch.Tensor):
@@ -419,6 +430,16 @@ class CameraFaceCapture:
         if not picked:
             return picked, [], torch.empty((0, S, S, 3), dtype=torch.uint8, device=self.device)
         dev = clip[picked].to(self.device).contiguous()
+        if getattr(self, "device_chain", False):
+            from .face_recognition import chain_faces, device_chain
+            host, _gate, crops = device_chain(p.detector, p.aligner, p.quality_filter, dev)
+            out = []
+            for f in range(len(picked)):
+                faces = chain_faces(p.quality_filter, host, f)
+                for x in faces:
+                    x["crop_row"] = x.pop("slot")
+                out.append(faces)
+            return picked, out, crops
         if hasattr(p.detector, "detect_batch"):
             per_frame = p.detector.detect_batch(dev)
         else:  # the reference's detector contract: one host image at a time

@@ -194,6 +194,201 @@ class FaceQualityFilter:
                 return False, m
         return True, m
 
+    def gate_device(self, dets: torch.Tensor, counts, ok=None, blur=None, out: Optional[Dict] = None) -> Dict:
+        """``is_valid`` for every slot of a batch of frames, ``process_numpy``'s order per frame and the
+        packed face lists, on the device and without a synchronisation (``fr_quality_gate_device``):
+        dets float32 [n,F,15] (``detect_device``), counts int32 [n] or None, ok uint8 [n,F]
+        (``align_device``) or None, blur float64 [n,F] or [n*F] (``blur_scores_device``) or None ->
+        a dict of device tensors: stage uint8 [n,F] (``GATE_*``), metrics float64 [n,F,5] (det_score,
+        blur_score, yaw, pitch, roll), bbox int32 [n,F,4], rank int32 [n,F], rows int32 [n*F],
+        frame_offsets int32 [n+1], valid_slots int32 [n*F], n_valid int32 [1].  ``out``: a dict from
+        an earlier call whose tensors are written again (for graph capture).  The values are
+        ``quality_gate_host``'s; what that means against ``is_valid`` is stated there."""
+        return self._ops.handle.quality_gate_device(dets, counts, ok, blur, _gate_config(self), out)
+
+    def metrics_from_gate(self, stage, metrics_row, bbox_row, blur_checked: Optional[bool] = None) -> Dict:
+        """The ``quality_metrics`` dict ``is_valid`` returns, rebuilt from one slot of the gate's
+        outputs: the same keys in the same insertion order for that stage (the early exit) and the
+        same types -- det_score a Python float, face_size np.int32, the angles np.float32, blur_score
+        np.float64.  ``blur_checked``: whether the gate ran its blur test (default: ``check_blur``;
+        False for a gate that ran without blur scores)."""
+        stage = int(stage)
+        if stage == GATE_NOT_LIVE:
+            raise ValueError("the slot is not live")
+        m: Dict = {"det_score": float(metrics_row[0])}
+        if stage == GATE_DET_SCORE:
+            return m
+        b = np.asarray(bbox_row, np.int32)
+        m["face_size"] = min(b[2] - b[0], b[3] - b[1])
+        if stage == GATE_FACE_SIZE:
+            return m
+        m["yaw"], m["pitch"], m["roll"] = (np.float32(metrics_row[k]) for k in (2, 3, 4))
+        if stage == GATE_POSE:
+            return m
+        if self.check_blur if blur_checked is None else blur_checked:
+            m["blur_score"] = np.float64(metrics_row[1])
+        return m
+
+
+GATE_MAX_FACES = 1024  # FR_GATE_MAX_FACES
+GATE_VALID, GATE_DET_SCORE, GATE_FACE_SIZE, GATE_POSE, GATE_BLUR, GATE_FIT, GATE_NOT_LIVE = 0, 1, 2, 3, 4, 5, 255
+_GATE_CONFIG_KEYS = ("min_det_score", "min_face_size", "max_yaw", "max_pitch", "max_roll", "blur_threshold")
+
+
+def _gate_config(config) -> Dict:
+    """A ``FaceQualityFilter`` or a dict of its constructor arguments -> the seven fields of
+    ``fr_gate_config``; ``ValueError`` for a limit that is not finite or lies beyond +-FLT_MAX."""
+    if isinstance(config, FaceQualityFilter):
+        c = {k: getattr(config, k) for k in _GATE_CONFIG_KEYS + ("check_blur",)}
+    else:
+        c = dict(min_det_score=0.6, min_face_size=60, max_yaw=45, max_pitch=30, max_roll=30, check_blur=True,
+                 blur_threshold=100)
+        c.update(config or {})
+    out = {k: float(c[k]) for k in _GATE_CONFIG_KEYS}
+    fmax = float(np.finfo(np.float32).max)
+    for k, v in out.items():
+        if not -fmax <= v <= fmax:  # a NaN fails both
+            raise ValueError(f"{k} = {v} is not finite or lies beyond +-FLT_MAX")
+    out["check_blur"] = bool(c["check_blur"])
+    return out
+
+
+def quality_gate_host(dets, counts, ok, blur, config, max_faces: Optional[int] = None):
+    """The contract of ``fr_quality_gate_device`` (include/frhip.h) in vectorised numpy: the gate of
+    ``FaceQualityFilter.is_valid`` per slot, the order of ``process_numpy`` per frame and the packed
+    face lists, for dets float32 [n,F,15] (x0 y0 x1 y1 score, 5 x (x, y)), counts int32 [n] or None
+    (every slot live), ok uint8 [n,F] or None, blur float64 [n,F] or None; ``config`` a
+    ``FaceQualityFilter`` or a dict of its arguments.
+
+    -> (stage uint8 [n,F], metrics float64 [n,F,5] = det_score, blur_score, yaw, pitch, roll,
+    bbox int32 [n,F,4], rank int32 [n,F], rows int32 [n*F], frame_offsets int32 [n+1],
+    valid_slots int32 [n*F], n_valid int32 [1]).
+
+    Everything is float32 / float64 IEEE arithmetic as ``is_valid`` does it, except that arctan2 and
+    arcsin are taken in double and rounded to float32: numpy's own float32 forms are a few ulp off
+    the correctly rounded value and differ between hosts, so the contract names the value they
+    approximate.  Against ``is_valid`` on any numpy: pitch and everything else bitwise, yaw and roll
+    within 1e-4 degrees (yaw for |ratio| <= 0.95), the decision equal unless an angle lies that close
+    to its limit."""
+    d = np.ascontiguousarray(dets, dtype=np.float32)
+    if d.ndim != 3 or d.shape[2] != 15:
+        raise ValueError("dets must be float32 [n,F,15] detection rows")
+    n, F = d.shape[0], d.shape[1]
+    if max_faces is not None and int(max_faces) != F:
+        raise ValueError(f"dets have {F} slots per frame, max_faces is {max_faces}")
+    if not 1 <= F <= GATE_MAX_FACES:
+        raise ValueError(f"max_faces must lie in [1, {GATE_MAX_FACES}]")
+    c = _gate_config(config)
+    live_n = np.full(n, F, np.int64) if counts is None else np.clip(np.asarray(counts, np.int64).reshape(n), 0, F)
+    live = np.arange(F)[None, :] < live_n[:, None]
+    with np.errstate(all="ignore"):
+        bbox = d[..., :4].astype(np.int32)
+        score = d[..., 4].astype(np.float64)
+        size = np.minimum(bbox[..., 2] - bbox[..., 0], bbox[..., 3] - bbox[..., 1])
+        f32 = np.float32
+        lex, ley, rex, rey, nx, ny, lmy, rmy = (d[..., k] for k in (5, 6, 7, 8, 9, 10, 12, 14))
+        ecx, ecy = (lex + rex) / f32(2), (ley + rey) / f32(2)
+        dx, dy = rex - lex, rey - ley
+        dist = np.sqrt(dx * dx + dy * dy)
+        ratio = (nx - ecx) / dist
+        ratio = np.where(ratio < -1, f32(-1), np.where(ratio > 1, f32(1), ratio)).astype(f32)  # a NaN stays
+        K = f32(180) / f32(np.pi)
+        roll = np.arctan2(dy.astype(np.float64), dx.astype(np.float64)).astype(f32) * K
+        yaw = np.arcsin(ratio.astype(np.float64)).astype(f32) * K * f32(2)
+        pitch = ((ny - ecy) / ((lmy + rmy) / f32(2) - ecy) - f32(0.5)) * f32(60)
+        assert roll.dtype == yaw.dtype == pitch.dtype == f32
+        fail_score = score < c["min_det_score"]
+        fail_size = size.astype(np.float64) < c["min_face_size"]
+        fail_pose = ((np.abs(yaw) > f32(c["max_yaw"])) | (np.abs(pitch) > f32(c["max_pitch"]))
+                     | (np.abs(roll) > f32(c["max_roll"])))
+        check_blur = c["check_blur"] and blur is not None
+        b = np.asarray(blur, np.float64).reshape(n, F) if check_blur else np.zeros((n, F))
+        fail_blur = (b < c["blur_threshold"]) if check_blur else np.zeros((n, F), bool)
+        fit = np.ones((n, F), bool) if ok is None else np.asarray(ok).reshape(n, F) != 0
+    stage = np.select([~live, fail_score, fail_size, fail_pose, fail_blur, ~fit],
+                      [GATE_NOT_LIVE, GATE_DET_SCORE, GATE_FACE_SIZE, GATE_POSE, GATE_BLUR, GATE_FIT],
+                      GATE_VALID).astype(np.uint8)
+    posed = live & ~fail_score & ~fail_size          # the pose angles were computed
+    blurred = posed & ~fail_pose & check_blur        # the blur score was recorded
+    metrics = np.zeros((n, F, 5))
+    metrics[..., 0] = np.where(live, score, 0.0)
+    metrics[..., 1] = np.where(blurred, b, 0.0)
+    for k, a in ((2, yaw), (3, pitch), (4, roll)):
+        metrics[..., k] = np.where(posed, a.astype(np.float64), 0.0)
+    bbox = np.where(live[..., None], bbox, 0).astype(np.int32)
+    with np.errstate(all="ignore"):
+        key = score * np.where(blurred, b, 1000.0)
+    rank = np.full((n, F), -1, np.int32)
+    rows = np.full(n * F, -1, np.int32)
+    valid_slots = np.full(n * F, -1, np.int32)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum(live_n)
+    for f in range(n):
+        m = int(live_n[f])
+        order = np.argsort(-key[f, :m], kind="stable")  # descending, equal keys by ascending slot
+        rank[f, order] = np.arange(m, dtype=np.int32)
+        rows[offsets[f]:offsets[f] + m] = f * F + order
+    packed = rows[:offsets[n]]
+    good = packed[stage.reshape(-1)[packed] == GATE_VALID]
+    valid_slots[:good.size] = good
+    return stage, metrics, bbox, rank, rows, offsets, valid_slots, np.array([good.size], np.int32)
+
+
+def tensors_to_host(tensors: Dict[str, torch.Tensor]) -> Dict[str, np.ndarray]:
+    """Device tensors -> host arrays of the same shapes and types in ONE copy (and one
+    synchronisation): their bytes are concatenated on the device, widest element type first."""
+    items = sorted(tensors.items(), key=lambda kv: -kv[1].element_size())
+    parts = [t.contiguous().view(-1).view(torch.uint8) for _k, t in items]
+    host = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, np.uint8)
+    out, at = {}, 0
+    for (k, t), p in zip(items, parts):
+        out[k] = host[at:at + p.numel()].view(torch.empty(0, dtype=t.dtype).numpy().dtype).reshape(tuple(t.shape))
+        at += p.numel()
+    return out
+
+
+def device_chain(detector, aligner, quality_filter, frames: torch.Tensor, max_faces: Optional[int] = None,
+                 with_dets: bool = True):
+    """Frames in HBM to gated, ranked faces in HBM: detect_device -> align_device ->
+    blur_scores_device -> gate_device back to back with ``max_faces`` slots per frame (default: the
+    detector's), then ONE copy of the per-slot outputs.  frames: uint8 [n,H,W,3] on the device ->
+    ``(host, gate, crops)``: ``host`` the gate's outputs, ``counts`` and (``with_dets``) ``dets`` as
+    host arrays, ``gate`` the gate's device tensors, ``crops`` uint8 [n*F,S,S,3] on the device, one
+    per slot (all-zero where the slot is not live or its fit was refused).  Needs the GPU
+    ``FaceDetector``: a detector without ``detect_device`` raises TypeError.  A frame over the
+    detector's 4096-candidate limit raises the ``NotImplementedError`` ``FaceDetector.detect`` raises."""
+    model = getattr(detector, "model", None)
+    if not hasattr(model, "detect_device"):
+        raise TypeError("the device chain runs the GPU FaceDetector (detect_device); this detector has none")
+    n = frames.shape[0]
+    F = detector.max_faces if max_faces is None else int(max_faces)
+    S = aligner.output_size
+    dets, counts = model.detect_device(frames, detector.det_thresh, F)
+    crops, _, ok = aligner._ops.handle.align_device(frames, dets, counts, S)
+    crops = crops.view(n * F, S, S, 3)
+    blur = quality_filter._ops.handle.blur_scores_device(crops) if quality_filter.check_blur else None
+    gate = quality_filter.gate_device(dets, counts, ok, blur)
+    host = tensors_to_host({**gate, "counts": counts, **({"dets": dets} if with_dets else {})})
+    for f in np.flatnonzero(host["counts"] < 0):
+        raise NotImplementedError(f"frame {f} has more than 4096 anchors above det_thresh (limit 4096)")
+    return host, gate, crops
+
+
+def chain_faces(quality_filter, host: Dict[str, np.ndarray], f: int) -> List[Dict]:
+    """Frame ``f`` of ``device_chain``'s host outputs as ``process_numpy(frame, return_all=True)``
+    lists it (descending det_score x blur_score, equal keys in detection order), each dict with
+    ``'slot'`` (the index of its crop) in place of ``'aligned_face'``."""
+    F = host["stage"].shape[1]
+    out = []
+    for slot in host["rows"][host["frame_offsets"][f]:host["frame_offsets"][f + 1]]:
+        i = int(slot) - f * F
+        stage = host["stage"][f, i]
+        q = quality_filter.metrics_from_gate(stage, host["metrics"][f, i], host["bbox"][f, i])
+        out.append({"slot": int(slot), "bbox": host["bbox"][f, i].copy(),
+                    "landmarks": host["dets"][f, i, 5:15].reshape(5, 2).copy(), "det_score": q["det_score"],
+                    "quality_metrics": q, "is_valid": bool(stage == GATE_VALID)})
+    return out
+
 
 def load_image_rgb(path: str) -> Optional[np.ndarray]:
     """cv2.cvtColor(cv2.imread(path), COLOR_BGR2RGB) through PIL: uint8 [H,W,3] RGB, or None when
@@ -376,6 +571,52 @@ class FaceProcessor:
         if gray:
             host = np.ascontiguousarray(host[..., 0])
         return self._gate(faces, host, blur, return_all)
+
+    def process_frames(self, frames, return_all: bool = False, max_faces: Optional[int] = None) -> List[List[Dict]]:
+        """``process_numpy`` for a batch of uint8 [n,H,W,3] RGB frames of one size (host array or
+        device tensor) with the whole chain on the device -> one list per frame of ``process_numpy``'s
+        dicts: detect_device -> align_device -> blur_scores_device -> gate_device run back to back
+        (``device_chain``), ONE packed copy brings the per-slot outputs over, and the crops that are
+        returned -- every live one (``return_all``) or the first valid one of each frame -- are gathered
+        on the device through the gate's ``rows`` / ``valid_slots`` before they are copied.  Crops of
+        every slot are held meanwhile: n * max_faces * S * S * 3 bytes (``max_faces`` defaults to the
+        detector's).
+
+        Against ``process_numpy`` per frame: the same faces in the same order, the same ``is_valid``
+        and crop bytes; metrics as ``quality_gate_host`` states (yaw and roll within 1e-4 degrees of
+        numpy's, all else bitwise).  A frame over the detector's 4096-candidate limit raises the
+        ``NotImplementedError`` ``FaceDetector.detect`` raises for it; a detection whose similarity fit
+        fails (where ``process_numpy`` raises) comes back ``is_valid: False`` with an all-zero crop."""
+        dev = self.aligner._ops.device
+        t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8))
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError("expected uint8 [n,H,W,3] RGB frames")
+        n = t.shape[0]
+        if n == 0:
+            return []
+        host, gate, crops = device_chain(self.detector, self.aligner, self.quality_filter, t.to(dev).contiguous(),
+                                         max_faces)
+        F = host["stage"].shape[1]
+        per_frame = [chain_faces(self.quality_filter, host, f) for f in range(n)]
+        if return_all:
+            total = int(host["frame_offsets"][n])
+            picked = gate["rows"][:total]  # the live slots, frame by frame in result order
+        else:
+            valid = host["valid_slots"][:int(host["n_valid"][0])]
+            first = np.flatnonzero(np.diff(valid // F, prepend=-1) != 0)  # the first valid slot of each frame
+            picked = gate["valid_slots"][torch.from_numpy(first).to(dev)]
+            keep = set(valid[first].tolist())
+            per_frame = [[x for x in faces if x["slot"] in keep] for faces in per_frame]
+        aligned = crops[picked.long()].cpu().numpy()
+        at = 0
+        for faces in per_frame:
+            for x in faces:
+                del x["slot"]
+                x["aligned_face"] = aligned[at]
+                at += 1
+        assert at == len(aligned)
+        return [[{k: x[k] for k in ("aligned_face", "bbox", "landmarks", "det_score", "quality_metrics", "is_valid")}
+                 for x in faces] for faces in per_frame]
 
     def _gate(self, faces: List[Dict], host: np.ndarray, blur, return_all: bool) -> List[Dict]:
         """The host gate, sort and result dicts of one image (face_recognition.py:192-216): ``host[i]``

@@ -227,8 +227,9 @@ class LiveFaceRecognition(AttendanceSession):
                  session_name=None, recognition_interval=30, max_recognition_attempts=3, frame_buffer_size=10,
                  enable_performance_monitoring=True, enable_gpu_monitoring=True, use_gpu=True, model_type="adaface",
                  architecture="ir_101", auto_snapshot=True, snapshot_interval=5.0, model_path=None, device=None,
-                 processor=None, embedder=None, gallery=None, verbose: bool = True):
+                 processor=None, embedder=None, gallery=None, verbose: bool = True, device_chain: bool = False):
         self.verbose = verbose
+        self.device_chain = bool(device_chain)  # process_clip: CameraFaceCapture's device chain per clip
         self._print("\n" + "=" * 70)
         self._print("INITIALIZING LIVE FACE RECOGNITION SYSTEM")
         self._print("=" * 70)
@@ -407,7 +408,8 @@ class LiveFaceRecognition(AttendanceSession):
             raise ValueError("timestamps: one list per clip")
         p = self.face_processor
         device = p.aligner._ops.device
-        shim = types.SimpleNamespace(processor=p, skip_frames=1, device=device)
+        shim = types.SimpleNamespace(processor=p, skip_frames=1, device=device,
+                                     device_chain=getattr(self, "device_chain", False))
         per_clip = []
         for c in clips:  # detect -> align -> blur -> gate, the crops left on the device
             if isinstance(c, torch.Tensor):

@@ -78,7 +78,8 @@ class RecognitionPipeline:
             out[i]["recognized"] = bool(m) and m[0][2] >= self.similarity_threshold
         return out
 
-    def recognize_frames(self, frames, top_k: int = 3, max_faces: Optional[int] = None) -> List[List[Dict]]:
+    def recognize_frames(self, frames, top_k: int = 3, max_faces: Optional[int] = None,
+                         gate: str = "host") -> List[List[Dict]]:
         """``recognize`` for a batch of frames, detection included: uint8 [n,H,W,3] RGB frames of one
         size (host array or device tensor) -> one list per frame of the dicts ``recognize(frame,
         detections)`` returns for the GPU detector's detections of that frame.
@@ -89,7 +90,17 @@ class RecognitionPipeline:
         host for the quality gate, and the valid crops are gathered on the device for one
         ``embed_match``.  A frame over the detector's 4096-candidate limit raises the
         ``NotImplementedError`` that ``FaceDetector.detect`` raises for it; a detection whose
-        similarity fit fails (where ``recognize`` raises) comes back ``is_valid: False``."""
+        similarity fit fails (where ``recognize`` raises) comes back ``is_valid: False``.
+
+        ``gate="device"`` runs the quality gate on the device as well (``fr_quality_gate_device``): the
+        one copy then brings the gate's per-slot outputs and the number of valid faces, the valid
+        crops are gathered through the gate's ``valid_slots`` without a host-built index, and the
+        dicts are rebuilt with ``metrics_from_gate``.  The same faces, ids and flags; yaw and roll as
+        ``quality_gate_host`` states them (within 1e-4 degrees of the host gate's); the valid crops
+        are embedded in the gate's order (per frame by descending det_score x blur_score), another
+        batch order, so scores agree within 1e-6."""
+        if gate not in ("host", "device"):
+            raise ValueError('gate must be "host" or "device"')
         dev = self.embedder.device
         if self.detector is None:
             self.detector = FaceDetector(device=dev)
@@ -108,6 +119,8 @@ class RecognitionPipeline:
         dets, counts = det.model.detect_device(t, det.det_thresh, F)
         crops, _, ok = self.aligner._ops.handle.align_device(t, dets, counts, S)
         crops = crops.view(n * F, S, S, 3)
+        if gate == "device":
+            return self._recognize_gated(dets, counts, ok, crops, n, F, top_k)
         blur = self.quality._ops.handle.blur_scores_device(crops) if self.quality.check_blur else dets.new_empty(
             0, dtype=torch.float64)
         parts = [blur.view(torch.uint8), dets.view(-1).view(torch.uint8), counts.view(torch.uint8), ok.view(-1)]
@@ -139,6 +152,38 @@ class RecognitionPipeline:
         for m, (f, i) in zip(res, valid):
             out[f][i]["matches"] = m
             out[f][i]["recognized"] = bool(m) and m[0][2] >= self.similarity_threshold
+        return out
+
+
+    def _recognize_gated(self, dets, counts, ok, crops, n: int, F: int, top_k: int) -> List[List[Dict]]:
+        """``recognize_frames`` from the aligned slots on, with the gate on the device."""
+        from .face_recognition import GATE_VALID, tensors_to_host
+        blur = self.quality._ops.handle.blur_scores_device(crops) if self.quality.check_blur else None
+        g = self.quality.gate_device(dets, counts, ok, blur)
+        # the chain's one copy and its one synchronisation
+        host = tensors_to_host({**{k: g[k] for k in ("stage", "metrics", "bbox", "valid_slots", "n_valid")},
+                                "counts": counts})
+        for f in range(n):
+            if host["counts"][f] < 0:
+                raise NotImplementedError(f"frame {f} has more than 4096 anchors above det_thresh (limit 4096)")
+        out: List[List[Dict]] = []
+        for f in range(n):
+            rows = []
+            for i in range(min(int(host["counts"][f]), F)):
+                stage = host["stage"][f, i]
+                q = self.quality.metrics_from_gate(stage, host["metrics"][f, i], host["bbox"][f, i])
+                rows.append({"bbox": host["bbox"][f, i].copy(), "det_score": q["det_score"], "quality_metrics": q,
+                             "is_valid": bool(stage == GATE_VALID), "matches": [], "recognized": False})
+            out.append(rows)
+        n_valid = int(host["n_valid"][0])
+        if not n_valid:
+            return out
+        sel = crops[g["valid_slots"][:n_valid].long()].contiguous()
+        res = self.gallery.match_resolved(n_valid, top_k, lambda h, k, idx, score: h.embed_match(sel, k, idx, score))
+        for m, slot in zip(res, host["valid_slots"][:n_valid]):
+            row = out[slot // F][slot % F]
+            row["matches"] = m
+            row["recognized"] = bool(m) and m[0][2] >= self.similarity_threshold
         return out
 
 

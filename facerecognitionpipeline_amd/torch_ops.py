@@ -34,7 +34,7 @@ from __future__ import annotations
 
 import itertools
 import threading
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -347,3 +347,31 @@ def blur_scores(crops: torch.Tensor) -> torch.Tensor:
 @blur_scores.register_fake
 def _(crops):
     return crops.new_empty((crops.shape[0],), dtype=torch.float64)
+
+
+# The quality gate behind them (fr_quality_gate_device): ``limits`` = min_det_score, min_face_size,
+# max_yaw, max_pitch, max_roll, blur_threshold; the outputs in _lib.GATE_OUTPUTS order.
+_GateOut = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                 torch.Tensor]
+
+
+@torch.library.custom_op("frhip::quality_gate", mutates_args=())
+def quality_gate(dets: torch.Tensor, counts: Optional[torch.Tensor], ok: Optional[torch.Tensor],
+                 blur: Optional[torch.Tensor], limits: List[float], check_blur: bool) -> _GateOut:
+    if dets.device.type != "cuda":
+        raise ValueError(f"dets are on {dets.device}: quality_gate runs on a HIP device (no CPU fallback)")
+    if len(limits) != 6:
+        raise ValueError("limits: min_det_score, min_face_size, max_yaw, max_pitch, max_roll, blur_threshold")
+    config = dict(zip(("min_det_score", "min_face_size", "max_yaw", "max_pitch", "max_roll", "blur_threshold"),
+                      limits), check_blur=check_blur)
+    out = utility_handle(dets.device).quality_gate_device(dets, counts, ok, blur, config)
+    return tuple(out[k] for k in _lib.GATE_OUTPUTS)
+
+
+@quality_gate.register_fake
+def _(dets, counts, ok, blur, limits, check_blur):
+    n, f = dets.shape[0], dets.shape[1]
+    new = dets.new_empty
+    return (new((n, f), dtype=torch.uint8), new((n, f, 5), dtype=torch.float64), new((n, f, 4), dtype=torch.int32),
+            new((n, f), dtype=torch.int32), new((n * f,), dtype=torch.int32), new((n + 1,), dtype=torch.int32),
+            new((n * f,), dtype=torch.int32), new((1,), dtype=torch.int32))

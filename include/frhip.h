@@ -613,6 +613,70 @@ int fr_align_device(fr_handle* h, const uint8_t* frames /* device [n_frames][hei
 int fr_blur_scores_device(fr_handle* h, const uint8_t* crops, int n, int height, int width, int channels,
                           double* scores /* device [n] */, void* stream);
 
+/* ---- The quality gate, the per-frame order and the packed face lists of
+ * FaceProcessor.process_numpy on the device: the link between the chain above and the embedder /
+ * the session kernels.  Asynchronous on `stream`, no synchronisation, no host read after return,
+ * capturable; allocates (n_frames ints) only when n_frames exceeds any earlier call's; any handle
+ * will do, finalised or not.
+ *
+ * Slot i of frame f (F = max_faces slots per frame) is live when i < min(counts[f], F); a negative
+ * count makes none live, counts == NULL all.  A live slot goes through FaceQualityFilter.is_valid's
+ * tests in is_valid's order and the first failing one is its stage; metrics the early exit never
+ * computes are stored as 0.0:
+ *   bbox       the C cast (truncation) of the row's four floats, d[:4].astype(np.int32); the floats
+ *              must lie inside int32's range
+ *   FR_GATE_DET_SCORE  (double)score < min_det_score
+ *   FR_GATE_FACE_SIZE  (double)min(x1 - x0, y1 - y0) < min_face_size, on bbox's ints
+ *   FR_GATE_POSE       compute_pose_angles in float32 operations, none contracted: dx, dy, the eye
+ *              and mouth centres as the reference forms them, dist = sqrtf(dx*dx + dy*dy),
+ *              ratio = clamp((nose_x - eye_cx) / dist, -1, 1) (a NaN stays),
+ *              roll = (float)atan2((double)dy, (double)dx) * K,
+ *              yaw = (float)asin((double)ratio) * K * 2.0f,
+ *              pitch = ((nose_y - eye_cy) / (mouth_cy - eye_cy) - 0.5f) * 60.0f, K = 180.0f / (float)pi;
+ *              fails when fabsf(angle) > (float)limit for any of the three (numpy 2 compares a
+ *              float32 with a Python scalar in float32); a NaN angle passes, as on the host.
+ *              Pitch is bitwise numpy's; yaw and roll are the correctly rounded float32 values up to
+ *              the double library's error at a rounding boundary, where numpy's own float32
+ *              functions are up to 4 ulp off and host-dependent (the device quality gate)
+ *   FR_GATE_BLUR       only with cfg->check_blur and blur != NULL: blur_score is recorded, then
+ *              blur < blur_threshold fails
+ *   FR_GATE_FIT        passed every test, but ok[slot] == 0 (fr_align_device refused the fit)
+ *   FR_GATE_VALID      otherwise.  A slot that is not live has stage FR_GATE_NOT_LIVE, rank -1, zeros.
+ * metrics: det_score, blur_score, yaw, pitch, roll, the angles as the doubles of their float32 values.
+ *
+ * rank[i]: the position of the slot in process_numpy's stable sort(reverse=True) over the frame's
+ * live slots: the number of live slots j with key_j > key_i, or key_j == key_i and j < i, with
+ * key = (double)score * (blur_score where recorded, else 1000.0).  Keys must not be NaN.
+ * frame_offsets: the exclusive prefix sum of the live counts, frame_offsets[n_frames] the total;
+ * rows[frame_offsets[f] + rank] = f * F + i, entries from the total on are -1;
+ * valid_slots: the slot indices f * F + i of stage FR_GATE_VALID in rows order, n_valid[0] their
+ * number, the tail -1.
+ *
+ * FR_ERR_INVALID_ARGUMENT: a NULL required buffer or cfg, max_faces outside [1, FR_GATE_MAX_FACES],
+ * n_frames < 0 or n_frames * max_faces >= 2^31, a limit that is not finite or lies beyond
+ * +-FLT_MAX.  n_frames == 0 is a no-op (nothing is written). */
+typedef struct {
+  double min_det_score, min_face_size, max_yaw, max_pitch, max_roll, blur_threshold;
+  int check_blur;
+} fr_gate_config;
+#define FR_GATE_MAX_FACES 1024 /* slots per frame */
+#define FR_GATE_VALID 0
+#define FR_GATE_DET_SCORE 1
+#define FR_GATE_FACE_SIZE 2
+#define FR_GATE_POSE 3
+#define FR_GATE_BLUR 4
+#define FR_GATE_FIT 5
+#define FR_GATE_NOT_LIVE 255
+int fr_quality_gate_device(fr_handle* h, const float* dets /* device [n][F][15], fr_detect_device's rows */,
+                           const int32_t* counts /* device [n] or NULL */,
+                           const uint8_t* ok /* device [n][F] (fr_align_device) or NULL */,
+                           const double* blur /* device [n][F] (fr_blur_scores_device) or NULL */, int n_frames,
+                           int max_faces, const fr_gate_config* cfg, uint8_t* stage /* device [n][F] */,
+                           double* metrics /* device [n][F][5] */, int32_t* bbox /* device [n][F][4] */,
+                           int32_t* rank /* device [n][F] */, int32_t* rows /* device [n*F] */,
+                           int32_t* frame_offsets /* device [n+1] */, int32_t* valid_slots /* device [n*F] */,
+                           int32_t* n_valid /* device [1] */, void* stream);
+
 /* Conv arithmetic of this handle.  FR_PRECISION_F32 (default): exact f32 products and f32
  * accumulation on fp32 MFMA -- the parity path.  FR_PRECISION_BF16X3 (opt-in fast mode):
  * each f32 operand split into bf16 hi + lo, x.y ~= hi.hi + hi.lo + lo.hi on bf16 MFMA with f32

@@ -169,6 +169,15 @@ int frt_fit_similarity(const float* src, const float* dst, int n, double* M);
  * With ms != NULL also the kernel's time between two HIP events of one more launch (milliseconds). */
 int frt_fit_similarity_device(const float* landmarks, int n, int out_size, double* M, uint8_t* ok, float* ms);
 
+/* fr_quality_gate_device on the CPU: the same per-slot arithmetic (csrc/gate_math.h, compiled for the
+ * host) and the same rank / pack rules, every buffer in host memory; no handle, no stream.  The
+ * same argument checks.  yaw and roll go through the host's double atan2 / asin, the device's
+ * through its own: they may differ by one float32 ulp at a rounding boundary, all else is bitwise. */
+int frt_quality_gate_host(const float* dets, const int32_t* counts, const uint8_t* ok, const double* blur,
+                          int n_frames, int max_faces, const fr_gate_config* cfg, uint8_t* stage, double* metrics,
+                          int32_t* bbox, int32_t* rank, int32_t* rows, int32_t* frame_offsets, int32_t* valid_slots,
+                          int32_t* n_valid);
+
 /* The detector stem's MaxPool2d(3, 2, 1) alone: x [B][H][W][C] -> y [B][(H+1)/2][(W+1)/2][C], NHWC
  * f32, C % 4 == 0, 16-byte aligned.  Asynchronous on stream. */
 int frt_maxpool3(const float* x, int B, int H, int W, int C, float* y, void* stream);
