@@ -438,6 +438,120 @@ int frt_fit_similarity_device(const float* landmarks, int n, int out_size, doubl
   return FR_OK;
 }
 
+int frt_warp_affine_images(const uint8_t* const* images, const int32_t* sizes, int n_images,
+                           const int32_t* face_image, const double* tforms, int n_faces, int out_size, uint8_t* out,
+                           void* stream) {
+  // fr_align_images' checks and descriptors, the maps the caller's instead of fitted ones
+  if (n_faces < 0 || n_images < 0 || out_size <= 0 || out_size > 1024 ||
+      (n_faces > 0 && (!images || !sizes || !tforms || !face_image || !out)))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_warp_affine_images: bad arguments");
+  if (n_faces == 0) return FR_OK;
+  for (int i = 0; i < n_images; ++i)
+    if (!images[i] || sizes[2 * i] <= 0 || sizes[2 * i + 1] <= 0)
+      return fail(nullptr, FR_ERR_INVALID_ARGUMENT,
+                  "frt_warp_affine_images: image " + std::to_string(i) + " is NULL or has a side < 1");
+  std::vector<WarpFace> faces((size_t)n_faces);
+  for (int f = 0; f < n_faces; ++f) {
+    const int i = face_image[f];
+    if (i < 0 || i >= n_images)
+      return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_warp_affine_images: face " + std::to_string(f) +
+                                                        " names image " + std::to_string(i) + " of " +
+                                                        std::to_string(n_images));
+    faces[f].src = images[i];
+    faces[f].H = sizes[2 * i];
+    faces[f].W = sizes[2 * i + 1];
+    invert_affine(tforms + (size_t)f * 6, faces[f].minv);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bytes = faces.size() * sizeof(WarpFace);
+  WarpFace* dev = nullptr;
+  hipError_t e = hipMalloc((void**)&dev, bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(dev, faces.data(), bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_warp_affine_images(dev, n_faces, out_size, out, s);
+  const hipError_t es = hipStreamSynchronize(s);  // also before the free when a step failed
+  if (e == hipSuccess) e = es;
+  (void)hipFree(dev);
+  if (e != hipSuccess)
+    return fail(nullptr, FR_ERR_HIP, std::string("frt_warp_affine_images: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+namespace {
+// What launch_letterbox / launch_letterbox_images refuse, asked before anything is staged.
+bool letterbox_canvas_ok(int dw, int dh, const uint8_t* out) {
+  return dw >= 1 && dh >= 1 && (dw * 3LL) % 4 == 0 && (long long)dh * dw * 3 < (1ll << 31) && out &&
+         (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+}
+}  // namespace
+
+int frt_letterbox(const uint8_t* frames, int n, int H, int W, int new_w, int new_h, int dw, int dh, uint8_t* out,
+                  void* stream) {
+  if (n < 1 || !frames || H < 1 || W < 1 || new_w < 1 || new_h < 1 || new_w > dw || new_h > dh ||
+      !letterbox_canvas_ok(dw, dh, out))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_letterbox: bad arguments");
+  // setup_geometry's tables: [new_w][4] for x, then [new_h][4] for y
+  std::vector<int> host((size_t)(new_w + new_h) * 4, 0);
+  resize_axis_table(new_w, W, host.data());
+  resize_axis_table(new_h, H, host.data() + 4 * new_w);
+  hipStream_t s = (hipStream_t)stream;
+  int* tabs = nullptr;
+  hipError_t e = hipMalloc((void**)&tabs, host.size() * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpyAsync(tabs, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess)
+    e = launch_letterbox(frames, n, H, W, tabs, tabs + 4 * new_w, new_w, new_h, resize_simd_end(new_w * 3), dw, dh,
+                         out, s);
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(tabs);
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_letterbox: refused");
+  if (e != hipSuccess) return fail(nullptr, FR_ERR_HIP, std::string("frt_letterbox: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_letterbox_images(const uint8_t* const* images, const int32_t* sizes, const int32_t* new_sizes, int n, int dw,
+                         int dh, uint8_t* out, void* stream) {
+  if (n < 1 || !images || !sizes || !new_sizes || !letterbox_canvas_ok(dw, dh, out))
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_letterbox_images: bad arguments");
+  size_t ints = 0;
+  for (int i = 0; i < n; ++i) {
+    const int new_h = new_sizes[2 * i], new_w = new_sizes[2 * i + 1];
+    if (!images[i] || sizes[2 * i] < 1 || sizes[2 * i + 1] < 1 || new_w < 1 || new_h < 1 || new_w > dw || new_h > dh)
+      return fail(nullptr, FR_ERR_INVALID_ARGUMENT,
+                  "frt_letterbox_images: image " + std::to_string(i) + " is NULL or has a bad size");
+    ints += (size_t)(new_w + new_h) * 4;
+  }
+  // letterbox_images' staging: [n] LetterboxImage | tables, image i's x table then its y table
+  const size_t tab_off = (size_t)n * sizeof(LetterboxImage);
+  std::vector<char> host(tab_off + ints * sizeof(int), 0);
+  auto* im = reinterpret_cast<LetterboxImage*>(host.data());
+  int* tabs = reinterpret_cast<int*>(host.data() + tab_off);
+  int at = 0;
+  for (int i = 0; i < n; ++i) {
+    const int height = sizes[2 * i], width = sizes[2 * i + 1];
+    const int new_h = new_sizes[2 * i], new_w = new_sizes[2 * i + 1];
+    im[i] = LetterboxImage{images[i], width, new_w, new_h, resize_simd_end(new_w * 3), at, at + 4 * new_w};
+    resize_axis_table(new_w, width, tabs + im[i].xtab);
+    resize_axis_table(new_h, height, tabs + im[i].ytab);
+    at += (new_w + new_h) * 4;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* dev = nullptr;
+  hipError_t e = hipMalloc((void**)&dev, host.size());
+  if (e == hipSuccess) e = hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess)
+    e = launch_letterbox_images(reinterpret_cast<const LetterboxImage*>(dev),
+                                reinterpret_cast<const int*>(dev + tab_off), n, dw, dh, out, s);
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(dev);
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_letterbox_images: refused");
+  if (e != hipSuccess)
+    return fail(nullptr, FR_ERR_HIP, std::string("frt_letterbox_images: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+int frt_resize_simd_end(int row_elems) { return resize_simd_end(row_elems); }
+
 int frt_quality_gate_host(const float* dets, const int32_t* counts, const uint8_t* ok, const double* blur,
                           int n_frames, int max_faces, const fr_gate_config* cfg, uint8_t* stage, double* metrics,
                           int32_t* bbox, int32_t* rank, int32_t* rows, int32_t* frame_offsets, int32_t* valid_slots,

@@ -37,9 +37,14 @@ __device__ __forceinline__ WarpTap warp_tap(const double* m, const WarpRow& r, i
   const long long adx = (long long)__builtin_rint(m[0] * ox * 1024.0);
   const long long bdx = (long long)__builtin_rint(m[3] * ox * 1024.0);
   const long long X = (X0 + adx) >> 5, Y = (Y0 + bdx) >> 5;
+  // The position is 64-bit (a caller's map may put it anywhere: contract |position| <= 2^40 px);
+  // narrowing it would wrap a far tap back into the frame.  Saturated to +-2^30 it stays outside
+  // every frame (sx + 1 cannot overflow) and clamps to the same edge pixel under BORDER_REPLICATE.
+  constexpr long long FAR = 1ll << 30;
+  const long long sx = X >> 5, sy = Y >> 5;
   WarpTap t;
-  t.sx = (int)(X >> 5);
-  t.sy = (int)(Y >> 5);
+  t.sx = (int)(sx < -FAR ? -FAR : (sx > FAR ? FAR : sx));
+  t.sy = (int)(sy < -FAR ? -FAR : (sy > FAR ? FAR : sy));
   const int fx = (int)(X & 31), fy = (int)(Y & 31);
   t.w00 = (32 - fx) * (32 - fy) * 32;
   t.w01 = fx * (32 - fy) * 32;

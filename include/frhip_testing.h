@@ -169,6 +169,31 @@ int frt_fit_similarity(const float* src, const float* dst, int n, double* M);
  * With ms != NULL also the kernel's time between two HIP events of one more launch (milliseconds). */
 int frt_fit_similarity_device(const float* landmarks, int n, int out_size, double* M, uint8_t* ok, float* ms);
 
+/* warp_affine_images_kernel (the ragged warp of fr_align_images / fr_align_device) on caller-supplied
+ * FORWARD maps: tforms host double [n_faces][2][3], each inverted with the runtime's invert_affine
+ * into the WarpFace of its face exactly as fr_align_images fills it (images / sizes / face_image as
+ * fr_align_images takes them; out device uint8 [n_faces][S][S][3]).  The same argument checks as
+ * fr_align_images (FR_ERR_INVALID_ARGUMENT, out untouched).  Stages through a temporary device
+ * buffer and synchronises.  Contract domain of the warp kernels (csrc/warp_map.h): finite maps whose
+ * source positions stay within +-2^40 px; there the crop is bitwise oracle/align_ref.py's. */
+int frt_warp_affine_images(const uint8_t* const* images, const int32_t* sizes, int n_images,
+                           const int32_t* face_image, const double* tforms, int n_faces, int out_size, uint8_t* out,
+                           void* stream);
+/* letterbox_kernel alone: n frames uint8 [n][H][W][3] resized to new_w x new_h (cv2.resize INTER_LINEAR)
+ * into the top-left of zero dw x dh canvases, out [n][dh][dw][3].  The tables are
+ * resize_axis_table(new_w, W) then resize_axis_table(new_h, H) and simd_end =
+ * resize_simd_end(new_w * 3), laid out as the detector's setup_geometry lays them out.
+ * frt_letterbox_images: letterbox_images_kernel alone, image i of sizes[i] = (h, w) resized to
+ * new_sizes[i] = (new_h, new_w), descriptors and tables staged as the detector's letterbox_images
+ * stages them.  new_w > dw, new_h > dh, a side < 1 and what the launchers refuse (dw * 3 % 4 != 0, out
+ * not 4-byte aligned) are FR_ERR_INVALID_ARGUMENT with out untouched.  Both synchronise. */
+int frt_letterbox(const uint8_t* frames, int n, int H, int W, int new_w, int new_h, int dw, int dh, uint8_t* out,
+                  void* stream);
+int frt_letterbox_images(const uint8_t* const* images, const int32_t* sizes, const int32_t* new_sizes, int n, int dw,
+                         int dh, uint8_t* out, void* stream);
+/* The host's resize_simd_end: where the SSE2-rounded part of a resized row of row_elems bytes ends. */
+int frt_resize_simd_end(int row_elems);
+
 /* fr_quality_gate_device on the CPU: the same per-slot arithmetic (csrc/gate_math.h, compiled for the
  * host) and the same rank / pack rules, every buffer in host memory; no handle, no stream.  The
  * same argument checks.  yaw and roll go through the host's double atan2 / asin, the device's

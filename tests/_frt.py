@@ -76,8 +76,72 @@ def lib():
         L.frt_det_stem.argtypes = [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]
         L.frt_detector_postprocess.restype = _I
         L.frt_detector_postprocess.argtypes = [_P, _P, _I, ctypes.c_float, _P, ctypes.c_float, _I, _P, _P, _P]
+        L.frt_warp_affine_images.restype = _I
+        L.frt_warp_affine_images.argtypes = [_P, _P, _I, _P, _P, _I, _I, _P, _P]
+        L.frt_letterbox.restype = _I
+        L.frt_letterbox.argtypes = [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]
+        L.frt_letterbox_images.restype = _I
+        L.frt_letterbox_images.argtypes = [_P, _P, _P, _I, _I, _I, _P, _P]
+        L.frt_resize_simd_end.restype = _I
+        L.frt_resize_simd_end.argtypes = [_I]
         L._frt_ready = True
     return L
+
+
+def _image_arrays(images):
+    """A list of contiguous uint8 [H,W,3] cuda tensors -> (host pointer array uint64 [n], sizes int32 [n,2])."""
+    import numpy as np
+    for im in images:
+        assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3 and im.is_contiguous() and im.is_cuda
+    ptrs = np.array([im.data_ptr() for im in images], dtype=np.uint64)
+    sizes = np.array([[im.shape[0], im.shape[1]] for im in images], dtype=np.int32).reshape(-1, 2)
+    return ptrs, sizes
+
+
+def warp_affine_images(images, face_image, tforms, out_size, out=None):
+    """The ragged warp kernel on caller-supplied forward maps: images a list of uint8 [H,W,3] cuda
+    tensors, face_image int [n], tforms float64 [n,2,3] -> uint8 [n,S,S,3] (pre-filled with 0xA5, or
+    the caller's `out`)."""
+    import numpy as np
+    ptrs, sizes = _image_arrays(images)
+    fi = np.ascontiguousarray(face_image, dtype=np.int32).reshape(-1)
+    tf = np.ascontiguousarray(tforms, dtype=np.float64).reshape(-1, 2, 3)
+    n, S = fi.shape[0], int(out_size)
+    assert tf.shape[0] == n
+    if out is None:
+        out = torch.full((n, max(S, 0), max(S, 0), 3), 0xA5, dtype=torch.uint8, device=images[0].device)
+    _lib.check(lib().frt_warp_affine_images(ptrs.ctypes.data, sizes.ctypes.data, len(images), fi.ctypes.data,
+                                            tf.ctypes.data, n, S, _p(out), torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def letterbox(frames, new_w, new_h, dw, dh, out):
+    """letterbox_kernel alone: frames uint8 [n,H,W,3] cuda -> the first n canvases of `out` (uint8 cuda,
+    at least n * dh * dw * 3 bytes, written in place so a test sees what lies behind them)."""
+    n, H, W = frames.shape[:3]
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and out.dtype == torch.uint8
+    assert dw < 1 or dh < 1 or out.numel() >= n * dh * dw * 3
+    _lib.check(lib().frt_letterbox(_p(frames), n, H, W, int(new_w), int(new_h), int(dw), int(dh), _p(out),
+                                   torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def letterbox_images(images, new_sizes, dw, dh, out):
+    """letterbox_images_kernel alone: images a list of uint8 [H,W,3] cuda tensors, new_sizes [(new_h,
+    new_w)] per image -> the first len(images) canvases of `out`."""
+    import numpy as np
+    ptrs, sizes = _image_arrays(images)
+    ns = np.ascontiguousarray(new_sizes, dtype=np.int32).reshape(-1, 2)
+    assert ns.shape[0] == len(images) and out.dtype == torch.uint8
+    assert dw < 1 or dh < 1 or out.numel() >= len(images) * dh * dw * 3
+    _lib.check(lib().frt_letterbox_images(ptrs.ctypes.data, sizes.ctypes.data, ns.ctypes.data, len(images), int(dw),
+                                          int(dh), _p(out), torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def resize_simd_end(row_elems):
+    """The host's split between SSE2 and scalar vertical rounding of a resized row (no GPU needed)."""
+    return int(lib().frt_resize_simd_end(int(row_elems)))
 
 
 def _p(t):

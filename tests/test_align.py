@@ -146,6 +146,74 @@ def test_pose_angles_of_frontal_template():
     assert abs(p["pitch"] - ((0.61 - 0.46) / (0.74 - 0.46) - 0.5) * 60) < 1e-4
 
 
+def test_warp_of_a_plane_stays_within_the_fixed_point_error_bound():
+    """On the plane 2x + 3y the bilinear sample is exact, so an interior pixel of the restatement
+    differs from the exact affine sample only by its own roundings: 0.5 of the output, and per axis
+    1/64 px of the 1/32-px position plus 1/1024 px of the two cvRounds, times the slopes 2 + 3:
+    0.5 + (1/64 + 1/1024) * 5 = 0.583 (worst seen: 0.580)."""
+    H, W, S = 40, 50, 32
+    yy, xx = np.mgrid[:H, :W]
+    img = (2 * xx + 3 * yy).astype(np.uint8)[..., None]
+    assert img.max() == 2 * (W - 1) + 3 * (H - 1) <= 255
+    bound = 0.5 + (1 / 64 + 1 / 1024) * (2 + 3)
+    rng = np.random.default_rng(2024)
+    oy, ox = np.mgrid[:S, :S]
+    worst, n_int = 0.0, 0
+    for _ in range(200):
+        s, th = rng.uniform(0.5, 2.0), rng.uniform(-np.pi, np.pi)
+        c = np.array([rng.uniform(10, W - 10), rng.uniform(10, H - 10)])
+        L = s * np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]])
+        Mi = np.concatenate([L, (c - L @ np.array([S / 2, S / 2]))[:, None]], axis=1)  # output centre -> c
+        M = A.invert_affine(Mi)
+        Mb = A.invert_affine(M)
+        px = Mb[0, 0] * ox + Mb[0, 1] * oy + Mb[0, 2]
+        py = Mb[1, 0] * ox + Mb[1, 1] * oy + Mb[1, 2]
+        X, Y = A.warp_maps(M, S)
+        sx, sy = X >> 5, Y >> 5
+        inside = (sx >= 0) & (sx + 1 < W) & (sy >= 0) & (sy + 1 < H)
+        got = A.warp_affine_linear(img, M, S)[..., 0].astype(np.float64)
+        err = np.abs(got - (2 * px + 3 * py))[inside]
+        n_int += int(inside.sum())
+        if err.size:
+            worst = max(worst, float(err.max()))
+    assert n_int > 200 * S * S // 4
+    assert worst <= bound, worst
+
+
+def test_far_translation_is_all_border_in_the_restatement():
+    """What the warp kernels are held to far outside the 32-bit range: the restatement keeps 64-bit
+    positions, so every tap is outside and the crop is the border value."""
+    img = np.random.default_rng(3).integers(1, 256, (5, 7, 3), dtype=np.uint8)
+    M = np.array([[1.0, 0, -(2 ** 32 + 5)], [0, 1.0, 0]])
+    X, Y = A.warp_maps(M, 17)
+    assert (X >> 5).min() >= 2 ** 32 and ((X >> 5).astype(np.int32) < 7).any()  # narrowed, it lands in the frame
+    assert (Y >> 5).tolist() == [[y] * 17 for y in range(17)]
+    assert not A.warp_affine_linear(img, M, 17).any()
+
+
+def test_letterbox_widths_cover_every_tail_of_the_simd_split():
+    """Portrait sources 128 x w, w = 1..16, letterbox to new_w = 5w: every residue of new_w mod 16 and
+    of the row's bytes mod 4.  The host's resize_simd_end must split each such row where the
+    restatement's loop (oracle/scrfd.py resize_linear_u8) does."""
+    from oracle import scrfd as R
+    from tests import _frt
+    tails = {}
+    for w in range(1, 17):
+        new_w, new_h, _ = R.letterbox_geometry(128, w)
+        assert (new_w, new_h) == (5 * w, 640)
+        row = new_w * 3
+        x = 0
+        while x <= row - 16:
+            x += 16
+        while x < row - 8:
+            x += 8
+        assert _frt.resize_simd_end(row) == x
+        assert 0 <= row - x <= 15 and (row - x <= 8 or x == 0)  # a scalar tail of at most 8 bytes (15: no SIMD part)
+        tails[new_w % 16] = row - x
+    assert sorted(tails) == list(range(16)) and {5 * w * 3 % 4 for w in range(1, 17)} == {0, 1, 2, 3}
+    assert len(set(tails.values())) >= 8
+
+
 # ---------------------------------------------------------------- GPU: kernels vs restatement
 @pytest.mark.gpu
 @pytest.mark.parametrize("S,n", [(112, 24), (224, 24), (112, 60)])  # n > 48: maps via device memory
