@@ -57,6 +57,13 @@
 // U is the MFMA's A operand (rows = couts) and V the B operand (columns = tiles), so the
 // accumulator of lane (tile l&15, row group l>>4) holds 4 consecutive couts of one tile.
 //   U: [36 xi][Cout/16][Cin/16][64 lane = 16 k + cout][4]
+//
+// Map: wino4_body is the kernel, in three branches by wave (transform waves of wide / tall items,
+// transform waves of the default item, MFMA waves with their two epilogues).  W4Shape<VAR> holds an
+// item shape's constants; the branches share half_patch_to_ring (B^T, partner exchange, ring
+// writes), ring_put (wait, store, publish), out_rows (rows pass of the output transform) and
+// load_residual8 (eight pixels' residual, either addressing).  Host: launch_wino4 decides mode,
+// shape, RMIX and grid once and picks the instance from W4_INSTANCES.
 #include <algorithm>
 #include <type_traits>
 #include <cmath>
@@ -258,6 +265,81 @@ __device__ __forceinline__ void at6q(const f4 (&m)[6], f4 (&o)[4]) {
   o[3] = __builtin_elementwise_fma(c8, m34, m12 + m[5]);
 }
 
+// Half a patch (the lane's 3 columns x 6 rows, two channels) to the ring: B^T down the columns,
+// the partner exchange, B^T along the lane's 3 rows and the 18 ds_write_b64 into slot g % NSLOT
+// (SLOTF floats each) at the lane's dst_off.
+template <int NSLOT, int SLOTF>
+__device__ __forceinline__ void half_patch_to_ring(f2 (&d)[6][3], float* ring, int g, int dst_off) {
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {  // the lane's columns: d[.][b] <- (B^T d)[.][b]
+    f2 c[6], o[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) c[a] = d[a][b];
+    bt6v(c, o);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) d[a][b] = o[a];
+  }
+  // partner exchange: swap(upper half of d[k][b], lower half of d[3+k][b]) leaves, in both
+  // halves, transform row 3h + k with column b in d[k][b] and column 3 + b in d[3+k][b]
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(d[k][b][e]),
+                                                        __float_as_uint(d[3 + k][b][e]), false, false);
+        d[k][b][e] = __uint_as_float(r[0]);
+        d[3 + k][b][e] = __uint_as_float(r[1]);
+      }
+  float* dst = ring + (g % NSLOT) * SLOTF + dst_off;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const f2 row[6] = {d[k][0], d[k][1], d[k][2], d[3 + k][0], d[3 + k][1], d[3 + k][2]};
+    f2 v[6];
+    bt6v(row, v);
+#pragma unroll
+    for (int b = 0; b < 6; ++b) *reinterpret_cast<f2*>(dst + (6 * k + b) * 256) = v[b];
+  }
+}
+
+// The hand-off of step g: stored (store()) into its ring slot once every MFMA wave has finished
+// reading step g - NSLOT (fre >= g - NSLOT + 1), then published (rdy[t] = g + 1).
+template <int NMW, int NSLOT, class Store>
+__device__ __forceinline__ void ring_put(const int* fre, int* rdy, int t, int lane, int g, int& fseen, int poll_max,
+                                         Store&& store) {
+  if (g - NSLOT + 1 > fseen) fseen = lds_wait_min<NMW>(fre, g - NSLOT + 1, poll_max);
+  store();
+  lds_publish(rdy + t, lane, g + 1);
+}
+
+// The rows pass of the output transform Y = A^T M A on a lane's 4 couts (each row frees 8
+// accumulator registers).  The columns pass stays with its two callers: the deferred epilogue
+// issues residual loads between the passes, and as a helper it cost the residual instances spills.
+__device__ __forceinline__ void out_rows(const f4 (&acc)[NXI], f4 (&z)[6][4]) {
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const f4 m6[6] = {acc[6 * a], acc[6 * a + 1], acc[6 * a + 2], acc[6 * a + 3], acc[6 * a + 4], acc[6 * a + 5]};
+    at6q(m6, z[a]);
+  }
+}
+
+// Residual loads of the tile's pixels [I0, I0 + 8): with the output's offsets oo, or (RMIX) with
+// offsets of the residual's own layout rblk (row_col_offsets: the caller's offset computation)
+template <int RMIX, int I0, class Offsets>
+__device__ __forceinline__ void load_residual8(f4 (&pres)[16], __amdgpu_buffer_rsrc_t rr, const int (&oo)[4][4],
+                                               Offsets&& row_col_offsets, bool rblk) {
+  if constexpr (RMIX != 0) {
+    int rro[4], rco[4];
+    row_col_offsets(rblk, rro, rco);
+#pragma unroll
+    for (int i = I0; i < I0 + 8; ++i) pres[i] = ld4(rr, (int)((unsigned)rro[i >> 2] + (unsigned)rco[i & 3]));
+  } else {
+#pragma unroll
+    for (int i = I0; i < I0 + 8; ++i) pres[i] = ld4(rr, oo[i >> 2][i & 3]);
+  }
+}
+
 // item index -> (tile block mb, cout block nb, K split): one XCD's contiguous run of items
 // covers GM tile blocks x all cout blocks, so the patches and U blocks it streams are shared
 // in its L2
@@ -305,17 +387,24 @@ constexpr int W4_WIDE = 1, W4_TALL = 2;  // item shapes (wino4_body's VAR)
 //     so all four MFMA waves do useful products (a 64-cout item leaves two of them on clamped
 //     weights); four transform waves of 8 tiles (two passes of 4).  A ring slot holds 32 tiles
 //     (two 16-tile planes), two slots in the LDS of four.
+template <int VAR>
+struct W4Shape {
+  static constexpr int NMW = VAR == W4_WIDE ? 6 : 4;             // MFMA waves
+  static constexpr int NTW = 8 - NMW;                            // transform waves
+  static constexpr int FTT = VAR == W4_TALL ? 2 * FT : FT;       // tiles per item
+  static constexpr int FNW = VAR == W4_TALL ? 32 : 16 * NMW;     // output channels per item
+  static constexpr int NBT = VAR == W4_TALL ? NBUF / 2 : NBUF;   // ring slots
+  static constexpr int SLOTF = (FTT / FT) * VSTEP;               // floats per ring slot
+  static constexpr int NGT = VAR == W4_TALL ? 6 : NGEO;          // geometry tables
+  static_assert(NGT > NBT + 2 && (NBT * SLOTF + NGT * FTT * GEOW + 8) * 4 <= 160 * 1024, "LDS layout");
+};
+
 template <bool PRE, int EPI, int MODE, int RMIX = 0, int VAR = 0>
 __device__ __forceinline__ void wino4_body(const Wino4Params& p, float* ring, const int bid, const int nblk) {
   constexpr bool SPLIT = MODE == 1;
-  constexpr int NMW = VAR == W4_WIDE ? 6 : 4;             // MFMA waves
-  constexpr int NTW = 8 - NMW;                            // transform waves
-  constexpr int FTT = VAR == W4_TALL ? 2 * FT : FT;       // tiles per item
-  constexpr int FNW = VAR == W4_TALL ? 32 : 16 * NMW;     // output channels per item
-  constexpr int NBT = VAR == W4_TALL ? NBUF / 2 : NBUF;   // ring slots
-  constexpr int SLOTF = (FTT / FT) * VSTEP;               // floats per ring slot
-  constexpr int NGT = VAR == W4_TALL ? 6 : NGEO;          // geometry tables
-  static_assert(NGT > NBT + 2 && (NBT * SLOTF + NGT * FTT * GEOW + 8) * 4 <= 160 * 1024, "LDS layout");
+  using S = W4Shape<VAR>;
+  constexpr int NMW = S::NMW, NTW = S::NTW, FTT = S::FTT, FNW = S::FNW, NBT = S::NBT, SLOTF = S::SLOTF,
+                NGT = S::NGT;
   static_assert(VAR == 0 || (!PRE && MODE == 0 && RMIX == 0), "wide / tall items: whole items, no pre-BN");
   __builtin_assume(bid >= 0 && bid < nblk && nblk <= 65535);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -431,44 +520,11 @@ __device__ __forceinline__ void wino4_body(const Wino4Params& p, float* ring, co
       }
       auto store = [&](Patch2& P, int g) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          f2 (&d)[6][3] = P.d[q];
-#pragma unroll
-          for (int b = 0; b < 3; ++b) {
-            f2 c[6], o[6];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) c[a] = d[a][b];
-            bt6v(c, o);
-#pragma unroll
-            for (int a = 0; a < 6; ++a) d[a][b] = o[a];
-          }
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-#pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(d[k][b][e]),
-                                                                __float_as_uint(d[3 + k][b][e]), false, false);
-                d[k][b][e] = __uint_as_float(r[0]);
-                d[3 + k][b][e] = __uint_as_float(r[1]);
-              }
-          float* dst = ring + (g % NBT) * SLOTF + dst_off[q];
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const f2 row[6] = {d[k][0], d[k][1], d[k][2], d[3 + k][0], d[3 + k][1], d[3 + k][2]};
-            f2 v[6];
-            bt6v(row, v);
-#pragma unroll
-            for (int b = 0; b < 6; ++b) *reinterpret_cast<f2*>(dst + (6 * k + b) * 256) = v[b];
-          }
-        }
+        for (int q = 0; q < 2; ++q) half_patch_to_ring<NBT, SLOTF>(P.d[q], ring, g, dst_off[q]);
       };
       int fseen = 0;
       auto put = [&](Patch2& P, int g) {
-        if (g - NBT + 1 > fseen) fseen = lds_wait_min<NMW>(fre, g - NBT + 1, p.poll_max);
-        store(P, g);
-        lds_publish(rdy + t, lane, g + 1);
+        ring_put<NMW, NBT>(fre, rdy, t, lane, g, fseen, p.poll_max, [&] { store(P, g); });
       };
       Patch2 pa, pb;
       load(pa);
@@ -635,37 +691,7 @@ __device__ __forceinline__ void wino4_body(const Wino4Params& p, float* ring, co
 #pragma unroll
           for (int b = 0; b < 3; ++b) d[a][b] = __builtin_elementwise_fma(trow, f2{P.colm[b], P.colm[b]}, d[a][b]);
         }
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {  // the lane's columns: d[.][b] <- (B^T d)[.][b]
-        f2 c[6], o[6];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) c[a] = d[a][b];
-        bt6v(c, o);
-#pragma unroll
-        for (int a = 0; a < 6; ++a) d[a][b] = o[a];
-      }
-      // partner exchange: swap(upper half of d[k][b], lower half of d[3+k][b]) leaves, in both
-      // halves, transform row 3h + k with column b in d[k][b] and column 3 + b in d[3+k][b]
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(d[k][b][e]),
-                                                            __float_as_uint(d[3 + k][b][e]), false, false);
-            d[k][b][e] = __uint_as_float(r[0]);
-            d[3 + k][b][e] = __uint_as_float(r[1]);
-          }
-      float* dst = ring + (g % NBUF) * VSTEP + dst_off;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const f2 row[6] = {d[k][0], d[k][1], d[k][2], d[3 + k][0], d[3 + k][1], d[3 + k][2]};
-        f2 v[6];
-        bt6v(row, v);
-#pragma unroll
-        for (int b = 0; b < 6; ++b) *reinterpret_cast<f2*>(dst + (6 * k + b) * 256) = v[b];
-      }
+      half_patch_to_ring<NBUF, VSTEP>(d, ring, g, dst_off);
     };
     // Step g is stored into ring slot g % NBUF once every MFMA wave has finished reading step
     // g - NBUF (fre >= g - NBUF + 1), then published (rdy[t] = g + 1).  Its patch loads were
@@ -673,11 +699,10 @@ __device__ __forceinline__ void wino4_body(const Wino4Params& p, float* ring, co
     // loads' issue.  Loads run past the stream's end unconditionally (they fetch whatever the
     // clamped geometry names and are never stored): a branch around them would make the
     // compiler's wait-count tracking wait for the freshly issued loads before the store.
+    // (ring_put: the wait, the store and the publish.)
     int fseen = 0;
     auto put = [&](Patch& P, int g) {
-      if (g - NBUF + 1 > fseen) fseen = lds_wait_min<NMW>(fre, g - NBUF + 1, p.poll_max);
-      store(P, g);
-      lds_publish(rdy + t, lane, g + 1);
+      ring_put<NMW, NBUF>(fre, rdy, t, lane, g, fseen, p.poll_max, [&] { store(P, g); });
     };
     if (G <= 2) {
       // one or two K-steps (split-K serving launches): no loads past the stream's end.  The
@@ -890,20 +915,8 @@ __device__ __forceinline__ void wino4_body(const Wino4Params& p, float* ring, co
       // of output rows 0-1 in flight during the column pass, then rows 2-3
       auto transform_to_pv = [&]() {
         f4 z[6][4];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          const f4 m6[6] = {acc[6 * a], acc[6 * a + 1], acc[6 * a + 2], acc[6 * a + 3], acc[6 * a + 4], acc[6 * a + 5]};
-          at6q(m6, z[a]);
-        }
-        if constexpr (DRES && RMIX) {
-          int rro[4], rco[4];
-          row_col_offsets(rblk, rro, rco);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) pres[i] = ld4(rr, (int)((unsigned)rro[i >> 2] + (unsigned)rco[i & 3]));
-        } else if constexpr (DRES) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) pres[i] = ld4(rr, oo[i >> 2][i & 3]);
-        }
+        out_rows(acc, z);
+        if constexpr (DRES) load_residual8<RMIX, 0>(pres, rr, oo, row_col_offsets, rblk);
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
           const f4 c6[6] = {z[0][x], z[1][x], z[2][x], z[3][x], z[4][x], z[5][x]};
@@ -914,15 +927,7 @@ __device__ __forceinline__ void wino4_body(const Wino4Params& p, float* ring, co
         }
       };
       auto set_pending = [&]() {
-        if constexpr (DRES && RMIX) {
-          int rro[4], rco[4];
-          row_col_offsets(rblk, rro, rco);
-#pragma unroll
-          for (int i = 8; i < 16; ++i) pres[i] = ld4(rr, (int)((unsigned)rro[i >> 2] + (unsigned)rco[i & 3]));
-        } else if constexpr (DRES) {
-#pragma unroll
-          for (int i = 8; i < 16; ++i) pres[i] = ld4(rr, oo[i >> 2][i & 3]);
-        }
+        if constexpr (DRES) load_residual8<RMIX, 8>(pres, rr, oo, row_col_offsets, rblk);
 #pragma unroll
         for (int i = 0; i < 16; ++i) po[i] = oo[i >> 2][i & 3];
         psc = *reinterpret_cast<const f4*>(p.post_scale + cout0);
@@ -945,11 +950,7 @@ __device__ __forceinline__ void wino4_body(const Wino4Params& p, float* ring, co
     // ms, same box)
     if constexpr (SPLIT) {
       f4 z[6][4];
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        const f4 m6[6] = {acc[6 * a], acc[6 * a + 1], acc[6 * a + 2], acc[6 * a + 3], acc[6 * a + 4], acc[6 * a + 5]};
-        at6q(m6, z[a]);
-      }
+      out_rows(acc, z);
       const int slot = it.li * p.ksplit + it.split;
       const __amdgpu_buffer_rsrc_t sr = uniform_rsrc(p.part, (int)min(p.part_floats * 4, 0x7fffffffll));
 #pragma unroll
@@ -1200,64 +1201,59 @@ int w4_split_of(const Wino4Params& p, int n, int cus, int& ks_per) {
 }
 }  // namespace
 
+namespace {
+// The kernel instances: one row per (pre-BN, epilogue, MODE, RMIX, item shape); a split-K row
+// carries its fixup.
+using W4Kernel = void (*)(Wino4Params);
+using W4Fixup = void (*)(Wino4Params, int, int);
+struct W4Instance {
+  bool pre;
+  Epi epi;
+  int mode, rmix, shape;
+  W4Kernel kernel;
+  W4Fixup fixup;
+};
+const W4Instance W4_INSTANCES[] = {
+    // IR conv1: pre-BN (in the transform), BN, PReLU
+    {true, EPI_AFFINE_PRELU, 0, 0, 0, wino4_kernel<true, EPI_AFFINE_PRELU, 0>, nullptr},
+    {true, EPI_AFFINE_PRELU, 1, 0, 0, wino4_kernel<true, EPI_AFFINE_PRELU, 1>, wino4_part_fixup_kernel<EPI_AFFINE_PRELU>},
+    // IR conv2: BN + identity shortcut
+    {false, EPI_AFFINE_RES, 0, 0, 0, wino4_kernel<false, EPI_AFFINE_RES, 0>, nullptr},
+    {false, EPI_AFFINE_RES, 1, 0, 0, wino4_kernel<false, EPI_AFFINE_RES, 1>, wino4_part_fixup_kernel<EPI_AFFINE_RES>},
+    {false, EPI_AFFINE_RES, 0, 1, 0, wino4_kernel<false, EPI_AFFINE_RES, 0, 1>, nullptr},
+    {false, EPI_AFFINE_RES, 0, 2, 0, wino4_kernel<false, EPI_AFFINE_RES, 0, 2>, nullptr},
+    // SCRFD conv + BN + ReLU (zero slopes)
+    {false, EPI_AFFINE_PRELU, 0, 0, 0, wino4_kernel<false, EPI_AFFINE_PRELU, 0>, nullptr},
+    {false, EPI_AFFINE_PRELU, 1, 0, 0, wino4_kernel<false, EPI_AFFINE_PRELU, 1>, wino4_part_fixup_kernel<EPI_AFFINE_PRELU>},
+    {false, EPI_AFFINE_PRELU, 0, 0, W4_WIDE, wino4w_kernel<EPI_AFFINE_PRELU>, nullptr},
+    {false, EPI_AFFINE_PRELU, 0, 0, W4_TALL, wino4t_kernel<EPI_AFFINE_PRELU>, nullptr},
+    // SCRFD conv + BN / bias
+    {false, EPI_AFFINE, 0, 0, 0, wino4_kernel<false, EPI_AFFINE, 0>, nullptr},
+    {false, EPI_AFFINE, 1, 0, 0, wino4_kernel<false, EPI_AFFINE, 1>, wino4_part_fixup_kernel<EPI_AFFINE>},
+    {false, EPI_AFFINE, 0, 0, W4_WIDE, wino4w_kernel<EPI_AFFINE>, nullptr},
+    {false, EPI_AFFINE, 0, 0, W4_TALL, wino4t_kernel<EPI_AFFINE>, nullptr},
+    // SCRFD BasicBlock conv2 + BN + add + ReLU
+    {false, EPI_AFFINE_RES_PRELU, 0, 0, 0, wino4_kernel<false, EPI_AFFINE_RES_PRELU, 0>, nullptr},
+    {false, EPI_AFFINE_RES_PRELU, 1, 0, 0, wino4_kernel<false, EPI_AFFINE_RES_PRELU, 1>,
+     wino4_part_fixup_kernel<EPI_AFFINE_RES_PRELU>},
+    {false, EPI_AFFINE_RES_PRELU, 0, 0, W4_WIDE, wino4w_kernel<EPI_AFFINE_RES_PRELU>, nullptr},
+    {false, EPI_AFFINE_RES_PRELU, 0, 0, W4_TALL, wino4t_kernel<EPI_AFFINE_RES_PRELU>, nullptr},
+};
+}  // namespace
+
 hipError_t launch_wino4(const Wino4Params& p0, bool pre, Epi epi, hipStream_t s) {
   Wino4Params p = p0;
   if (!w4_setup(p, pre)) return hipErrorInvalidValue;
   const int KST = p.Cin / KC;
   const int nT = p.mblocks * p.nblocks;
-  const bool aligned = w4_aligned(p);
   const int cus = w4_cus();
-  const bool can_split = p.part && !p.no_split && aligned && KST > 1;
-  auto split_of = [&](int n, int& ks_per) { return w4_split_of(p, n, cus, ks_per); };
-  // Whole-item launch of n items from item0 (MODE 0), or split-K launch (MODE 1) + fixup.  (A
-  // stream-K tail for the part-empty last round of whole items -- IR-101 B = 256: stage 3 3.52
-  // rounds run as 4 -- was built in round 4 and measured neutral; two concurrent lanes fill that
-  // round instead: tools/w4_archive/, DESIGN.md section 4.)
-  Wino4Params pw = p;
-  auto whole = [&](int item0, int n) {
-    pw = p;
-    pw.item0 = item0;
-    pw.nitem = n;
-    pw.ksplit = 1;
-    pw.ks_per = KST;
-  };
-  auto splitk = [&](int item0, int n, int S, int ks_per) {
-    pw = p;
-    pw.item0 = item0;
-    pw.nitem = n;
-    pw.ksplit = S;
-    pw.ks_per = ks_per;
-  };
-#define FR_W4_LAUNCH(PRE_, EPI_, MODE_)                                                                     \
-  {                                                                                                         \
-    const int nit = pw.nitem * pw.ksplit;                                                                   \
-    hipLaunchKernelGGL((wino4_kernel<PRE_, EPI_, MODE_>), dim3(std::min(nit, cus)), dim3(512), 0, s, pw);   \
-    if (MODE_ == 1) /* 64-thread blocks: a serving grid's few items still spread over the CUs */          \
-      hipLaunchKernelGGL((wino4_part_fixup_kernel<EPI_>), dim3(FT * 16 * FN / 4 / 64, pw.nitem),     \
-                         dim3(64), 0, s, pw, KST, cus);                                                     \
-  }
+  const bool can_split = p.part && !p.no_split && w4_aligned(p) && KST > 1;
   // a residual whose layout differs from y's (p.blk: the seams between NHWC and channel-blocked
   // activations): whole-item launches run instances of their own (RMIX); a split-K
   // launch's fixup addresses the residual on its own anyway, so split-K is the usual one
-  const bool rmix = (((p.blk & W4_BLK_RES) != 0) != ((p.blk & W4_BLK_Y) != 0)) &&
-                    (epi == EPI_AFFINE_RES || epi == EPI_AFFINE_RES_PRELU);
-  if (rmix) {
-    if (pre || epi != EPI_AFFINE_RES) return hipErrorInvalidValue;
-    int ks_per = KST;
-    const int S = can_split && nT <= cus / 2 ? split_of(nT, ks_per) : 1;
-    if (S > 1) {
-      splitk(0, nT, S, ks_per);
-      FR_W4_LAUNCH(false, EPI_AFFINE_RES, 1)
-      return hipGetLastError();
-    }
-    whole(0, nT);
-    const dim3 grid(std::min(nT, cus));
-    if (p.blk & W4_BLK_Y)
-      hipLaunchKernelGGL((wino4_kernel<false, EPI_AFFINE_RES, 0, 1>), grid, dim3(512), 0, s, pw);
-    else
-      hipLaunchKernelGGL((wino4_kernel<false, EPI_AFFINE_RES, 0, 2>), grid, dim3(512), 0, s, pw);
-    return hipGetLastError();
-  }
+  const bool res_mixed = (((p.blk & W4_BLK_RES) != 0) != ((p.blk & W4_BLK_Y) != 0)) &&
+                         (epi == EPI_AFFINE_RES || epi == EPI_AFFINE_RES_PRELU);
+  if (res_mixed && (pre || epi != EPI_AFFINE_RES)) return hipErrorInvalidValue;
   // Wide items: a whole-item launch of a layer of 65..96 couts (the detector's 80-channel towers
   // and heads) as one 96-cout item per 16 tiles on wino4w_kernel, not a 64-cout item plus one with
   // three of its four MFMA waves idle (each with its own input transform).  A wide item costs
@@ -1269,56 +1265,40 @@ hipError_t launch_wino4(const Wino4Params& p0, bool pre, Epi epi, hipStream_t s)
   // about a 64-cout item's time each.
   const bool shape_epi = epi == EPI_AFFINE || epi == EPI_AFFINE_PRELU || epi == EPI_AFFINE_RES_PRELU;
   const bool wide = p.Cout > FN && p.Cout <= 96, tall = p.Cout <= 32;
-  if (p.shapes && !pre && shape_epi && (wide || tall) && (nT > cus || p.shapes == 2)) {
+  int shape = 0;
+  if (!res_mixed && p.shapes && !pre && shape_epi && (wide || tall) && (nT > cus || p.shapes == 2))
+    shape = wide ? W4_WIDE : W4_TALL;
+  // The mode: one launch of whole items (MODE 0: S = 1, nitem items of KST steps), or a split-K
+  // launch (MODE 1: S parts of ks_per steps per item) + its fixup.  (A
+  // stream-K tail for the part-empty last round of whole items -- IR-101 B = 256: stage 3 3.52
+  // rounds run as 4 -- was built in round 4 and measured neutral; two concurrent lanes fill that
+  // round instead: tools/w4_archive/, DESIGN.md section 4.)
+  int S = 1, ks_per = KST, nitem = nT;
+  if (shape) {
     if (tall) p.mblocks = (p.ntiles + 2 * FT - 1) / (2 * FT);
     p.nblocks = 1;
     p.nbg = std::max(1, std::min(p.mblocks, p.nbg_override > 0 ? p.nbg_override : 32));
-    whole(0, p.mblocks);
-    const dim3 grid(std::min(p.mblocks, cus));
-#define FR_W4_SHAPED(EPI_)                                                  \
-  if (wide)                                                                 \
-    hipLaunchKernelGGL((wino4w_kernel<EPI_>), grid, dim3(512), 0, s, pw);   \
-  else                                                                      \
-    hipLaunchKernelGGL((wino4t_kernel<EPI_>), grid, dim3(512), 0, s, pw);
-    if (epi == EPI_AFFINE) {
-      FR_W4_SHAPED(EPI_AFFINE)
-    } else if (epi == EPI_AFFINE_PRELU) {
-      FR_W4_SHAPED(EPI_AFFINE_PRELU)
-    } else {
-      FR_W4_SHAPED(EPI_AFFINE_RES_PRELU)
-    }
-#undef FR_W4_SHAPED
+    nitem = p.mblocks;
+  } else if (can_split && nT <= cus / 2) {
+    // small grid (serving batches): every item's K loop split
+    S = w4_split_of(p, nT, cus, ks_per);
+  }
+  // else whole items.  (Running a part-empty last round as a split-K launch of its own was
+  // measured neutral: stage 2, 6 rounds + 32 items, 244.6 -> 245.8 us; the short launch and
+  // its fixup cost about the round they save.)
+  const int mode = S > 1 ? 1 : 0;
+  const int rmix = res_mixed && mode == 0 ? ((p.blk & W4_BLK_Y) ? 1 : 2) : 0;
+  p.item0 = 0;
+  p.nitem = nitem;
+  p.ksplit = S;
+  p.ks_per = ks_per;
+  for (const W4Instance& in : W4_INSTANCES) {
+    if (in.pre != pre || in.epi != epi || in.mode != mode || in.rmix != rmix || in.shape != shape) continue;
+    hipLaunchKernelGGL(in.kernel, dim3(std::min(nitem * S, cus)), dim3(512), 0, s, p);
+    if (in.fixup)  // 64-thread blocks: a serving grid's few items still spread over the CUs
+      hipLaunchKernelGGL(in.fixup, dim3(FT * 16 * FN / 4 / 64, nitem), dim3(64), 0, s, p, KST, cus);
     return hipGetLastError();
   }
-#define FR_W4_CASE(PRE_, EPI_)                                                                              \
-  if (pre == PRE_ && epi == EPI_) {                                                                         \
-    int ks_per = KST;                                                                                       \
-    if (can_split && nT <= cus / 2) {                                                                       \
-      /* small grid (serving batches): every item's K loop split */                                         \
-      const int S = split_of(nT, ks_per);                                                                   \
-      if (S > 1) {                                                                                          \
-        splitk(0, nT, S, ks_per);                                                                           \
-        FR_W4_LAUNCH(PRE_, EPI_, 1)                                                                         \
-      } else {                                                                                              \
-        whole(0, nT);                                                                                       \
-        FR_W4_LAUNCH(PRE_, EPI_, 0)                                                                         \
-      }                                                                                                     \
-    } else {                                                                                                \
-      /* whole items.  (Running a part-empty last round as a split-K launch of its own was      */          \
-      /* measured neutral: stage 2, 6 rounds + 32 items, 244.6 -> 245.8 us; the short launch and  */          \
-      /* its fixup cost about the round they save.)                                               */          \
-      whole(0, nT);                                                                                         \
-      FR_W4_LAUNCH(PRE_, EPI_, 0)                                                                           \
-    }                                                                                                       \
-    return hipGetLastError();                                                                               \
-  }
-  FR_W4_CASE(true, EPI_AFFINE_PRELU)       // IR conv1: pre-BN (in the transform), BN, PReLU
-  FR_W4_CASE(false, EPI_AFFINE_RES)        // IR conv2: BN + identity shortcut
-  FR_W4_CASE(false, EPI_AFFINE_PRELU)      // SCRFD conv + BN + ReLU (zero slopes)
-  FR_W4_CASE(false, EPI_AFFINE)            // SCRFD conv + BN / bias
-  FR_W4_CASE(false, EPI_AFFINE_RES_PRELU)  // SCRFD BasicBlock conv2 + BN + add + ReLU
-#undef FR_W4_CASE
-#undef FR_W4_LAUNCH
   return hipErrorInvalidValue;
 }
 
