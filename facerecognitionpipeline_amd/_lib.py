@@ -68,6 +68,8 @@ _SIGNATURES = {
     "fr_align_images": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
     "fr_detect_device": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P]),
     "fr_align_device": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "fr_detect_images_device": (_I, [_P, _P, _P, _I, ctypes.c_float, _I, _P, _P, _P]),
+    "fr_align_images_device": (_I, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "fr_blur_scores_device": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "fr_quality_gate_device": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fr_set_precision": (_I, [_P, _I]),
@@ -169,6 +171,7 @@ class Handle:
         h = _P()
         idx = device.index if device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
+        self.max_batch = int(max_batch)  # for a detector: max_frames, the images of one chunk
         self.gallery_tag = None  # (owner, version) of the rows in HBM; see GalleryManager._sync_device
         self.samples_tag = None  # the same for the sample gallery; see GalleryManager._sync_samples
         check(self._lib.fr_create(architecture.encode(), model_type.encode(), idx, int(max_batch), ctypes.byref(h)))
@@ -757,6 +760,61 @@ class Handle:
                                         fi.ctypes.data, n, S, ptr(out) if n else None, tf.ctypes.data,
                                         stream_of(self.device)), self.h)
         return tf
+
+    def detect_images_device(self, images, det_thresh: float = 0.5, max_faces: int = 256, dets=None, counts=None):
+        """``detect_images`` with device outputs and no synchronisation (fr_detect_images_device): a
+        list of uint8 [H,W,3] RGB device tensors of different sizes -> (dets f32 [n,max_faces,15],
+        counts int32 [n]) on the device; rows i < min(counts[f], max_faces) are ``detect_images``',
+        ``counts[f] == -1`` marks an image over the 4096-candidate limit (where ``detect_images``
+        raises).  The resize tables are made on the device and the geometry travels in the kernel
+        arguments: nothing is staged.  ``dets`` / ``counts``: tensors to write; new ``dets`` are
+        zero-filled.  The images must stay alive until the stream has run the call."""
+        images = list(images)
+        for i, im in enumerate(images):
+            if isinstance(im, torch.Tensor):
+                self._require_device(f"image {i}", im)
+        kept, ptrs, sizes = self._image_list(images)
+        n, F = len(kept), max(int(max_faces), 0)
+        dets = self._out("dets", dets, (n, F, 15), torch.float32, zero=True)
+        counts = self._out("counts", counts, (n,), torch.int32)
+        check(self._lib.fr_detect_images_device(self.h, ptrs.ctypes.data, sizes.ctypes.data, n, float(det_thresh),
+                                                int(max_faces), ptr(dets) if n * F else None, ptr(counts),
+                                                stream_of(self.device)), self.h)
+        return dets, counts
+
+    def align_images_device(self, images, landmarks: torch.Tensor, counts, out_size: int, out=None, tforms=None,
+                            ok=None):
+        """``align_device`` with a source per image (fr_align_images_device): ``images`` a list of n
+        uint8 [H,W,3] device tensors of different sizes; ``landmarks`` float32 on the device, detection
+        rows [n,F,15] (read in place) or [n,F,5,2]; ``counts`` int32 [n] on the device or None (all
+        live) -> (crops uint8 [n,F,S,S,3], tforms f64 [n,F,2,3], ok uint8 [n,F]).  Slot (i, k) warps
+        image i; a slot with ok == 0 has an all-zero crop and a NaN tform.  No synchronisation."""
+        images = list(images)
+        for i, im in enumerate(images):
+            if isinstance(im, torch.Tensor):
+                self._require_device(f"image {i}", im)
+        kept, ptrs, sizes = self._image_list(images)
+        n, S = len(kept), int(out_size)
+        lm = landmarks
+        if (not isinstance(lm, torch.Tensor) or lm.dtype != torch.float32 or lm.dim() not in (3, 4)
+                or lm.shape[0] != n or tuple(lm.shape[2:]) not in ((15,), (5, 2))):
+            raise ValueError(f"landmarks must be float32 [{n},F,15] detection rows or [{n},F,5,2]")
+        self._require_device("landmarks", lm)
+        lm = lm.contiguous()
+        F = lm.shape[1]
+        rows = lm.dim() == 3
+        if counts is not None:
+            if counts.dtype != torch.int32 or tuple(counts.shape) != (n,) or not counts.is_contiguous():
+                raise ValueError(f"counts must be a contiguous int32 [{n}] tensor")
+            self._require_device("counts", counts)
+        out = self._out("out", out, (n, F, S, S, 3), torch.uint8)
+        tforms = self._out("tforms", tforms, (n, F, 2, 3), torch.float64)
+        ok = self._out("ok", ok, (n, F), torch.uint8)
+        lm_ptr = (ptr(lm) + (5 * 4 if rows else 0)) if n * F else None
+        check(self._lib.fr_align_images_device(self.h, ptrs.ctypes.data, sizes.ctypes.data, n, lm_ptr,
+                                               15 if rows else 10, ptr(counts), F, S, ptr(out), ptr(tforms), ptr(ok),
+                                               stream_of(self.device)), self.h)
+        return out, tforms, ok
 
     def resize_images(self, images, out: torch.Tensor) -> None:
         """``resize_crops`` for a list of uint8 [H,W,3] RGB device tensors of different sizes -> out uint8

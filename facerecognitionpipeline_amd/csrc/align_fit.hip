@@ -13,10 +13,9 @@
 
 namespace frhip {
 
-__global__ __launch_bounds__(64) void fit_similarity_kernel(FitSlots p) {
-  const int slot = blockIdx.x * 64 + threadIdx.x;
-  if (slot >= p.n_frames * p.max_faces) return;
-  const int f = slot / p.max_faces, i = slot - f * p.max_faces;
+// Slot `slot` = (f, i) of p, frame f being src of H x W (unused when p.faces is NULL).
+__device__ __forceinline__ void fit_slot(const FitSlots& p, int slot, int f, int i, const uint8_t* src, int H,
+                                         int W) {
   const bool live = i < (p.counts ? p.counts[f] : p.max_faces);  // a negative count: no slot
   double M[6];
   bool ok = false;
@@ -37,10 +36,10 @@ __global__ __launch_bounds__(64) void fit_similarity_kernel(FitSlots p) {
   }
   if (p.faces) {
     WarpFace w;
-    w.src = p.frames + (long long)f * p.H * p.W * 3;
+    w.src = src;
     // not ok: no tap of a 0 x 0 source is in range, so warp_pixel reads nothing and writes zeros
-    w.H = ok ? p.H : 0;
-    w.W = ok ? p.W : 0;
+    w.H = ok ? H : 0;
+    w.W = ok ? W : 0;
     if (ok) {
       invert_affine5(M, w.minv);
     } else {
@@ -51,12 +50,37 @@ __global__ __launch_bounds__(64) void fit_similarity_kernel(FitSlots p) {
   }
 }
 
+__global__ __launch_bounds__(64) void fit_similarity_kernel(FitSlots p) {
+  const int slot = blockIdx.x * 64 + threadIdx.x;
+  if (slot >= p.n_frames * p.max_faces) return;
+  const int f = slot / p.max_faces, i = slot - f * p.max_faces;
+  fit_slot(p, slot, f, i, p.frames + (long long)f * p.H * p.W * 3, p.H, p.W);
+}
+
+// The ragged form: frame f is p.images[f], a load per lane from the argument segment (no copy).
+__global__ __launch_bounds__(64) void fit_similarity_images_kernel(FitImageSlots p) {
+  const int slot = blockIdx.x * 64 + threadIdx.x;
+  if (slot >= p.s.n_frames * p.s.max_faces) return;
+  const int f = slot / p.s.max_faces, i = slot - f * p.s.max_faces;
+  const FitImage im = p.images[f];
+  fit_slot(p.s, slot, f, i, im.src, im.H, im.W);
+}
+
 hipError_t launch_fit_similarity(const FitSlots& p, hipStream_t s) {
   if (p.n_frames <= 0 || p.max_faces <= 0) return hipSuccess;
   const long long slots = (long long)p.n_frames * p.max_faces;
   if (slots >= (1ll << 31) || !p.landmarks || !p.ok || p.stride < 10 || (p.faces && !p.frames) || p.H < 0 || p.W < 0)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(fit_similarity_kernel, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_fit_similarity_images(const FitImageSlots& p, hipStream_t s) {
+  if (p.s.n_frames <= 0 || p.s.max_faces <= 0) return hipSuccess;
+  const long long slots = (long long)p.s.n_frames * p.s.max_faces;
+  if (slots >= (1ll << 31) || !p.s.landmarks || !p.s.ok || p.s.stride < 10 || p.s.n_frames > FIT_IMAGES_BY_VALUE)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fit_similarity_images_kernel, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, s, p);
   return hipGetLastError();
 }
 

@@ -8,6 +8,8 @@
 //                      zero det_w x det_h canvas, in OpenCV's fixed point (11-bit
 //                      coefficients from the host; SSE2 vertical rounding for the
 //                      vectorised part of each row, scalar rounding for its tail)
+//   resize_tables_kernel  those coefficients made on the device (fr_detect_images_device), bitwise
+//                      the host's: one entry per thread, resize_table.h's arithmetic
 //   resize_images_kernel  the same resize for the embedder: crops of different sizes to
 //                      112 x 112 (fr_resize_images / fr_embed_images, embed_forward.cpp)
 //   det_stem_kernel    blobFromImage ((x - 127.5) / 128, RGB) fused into conv3x3 s2
@@ -19,6 +21,7 @@
 //   nms_kernel         sort by (score desc, anchor asc), greedy IoU NMS (numpy f32
 //                      arithmetic of SCRFD.nms), one workgroup per frame
 #include "frhip_kernels.h"
+#include "resize_table.h"
 
 #pragma clang fp contract(off)
 
@@ -86,6 +89,41 @@ __global__ __launch_bounds__(256) void letterbox_images_kernel(const LetterboxIm
   const LetterboxImage im = imgs[f];
   reinterpret_cast<unsigned*>(out + (long long)f * dh * row)[e4] =
       letterbox_group(im.src, im.W, tabs + im.xtab, tabs + im.ytab, im.new_w, im.new_h, im.simd_end, row4, e4);
+}
+
+// The same with the descriptors by value in the kernel arguments (fr_detect_images_device): no
+// descriptor is staged, so the caller's host arrays are dead when the launch returns.  f is
+// uniform over a block, so c.im[f] is scalar loads from the argument segment.
+__global__ __launch_bounds__(256) void letterbox_images_args_kernel(LetterboxChunk c, const int* __restrict__ tabs,
+                                                                    int dw, int dh, uint8_t* __restrict__ out) {
+  const int f = blockIdx.y;
+  const int e4 = blockIdx.x * 256 + threadIdx.x;
+  const int row = dw * 3, row4 = row / 4;
+  if (e4 >= dh * row4) return;
+  const LetterboxImage im = c.im[f];
+  reinterpret_cast<unsigned*>(out + (long long)f * dh * row)[e4] =
+      letterbox_group(im.src, im.W, tabs + im.xtab, tabs + im.ytab, im.new_w, im.new_h, im.simd_end, row4, e4);
+}
+
+// The resize tables of a chunk's images, made where they are read: thread e of image f writes
+// entry e of the x table ([new_w][4] at tabs + xtab) or entry e - new_w of the y table ([new_h][4]
+// at tabs + ytab) as one 16-byte store, and the image's det_scale goes to scales[f], where
+// decode_kernel reads it.  raw[f], decode_kernel's candidate counter of the image, is zeroed here as
+// well: the chunk's first launch prepares everything its later ones count on, and the chain needs
+// no memset of its own.  launch_resize_tables checks every table against the arena's size.
+__global__ __launch_bounds__(256) void resize_tables_kernel(LetterboxChunk c, int* __restrict__ tabs,
+                                                            float* __restrict__ scales, int* __restrict__ raw) {
+  const int f = blockIdx.y;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  const LetterboxImage im = c.im[f];
+  if (e == 0 && scales) scales[f] = c.scale[f];
+  if (e == 0 && raw) raw[f] = 0;
+  if (e >= im.new_w + im.new_h) return;
+  const bool x = e < im.new_w;
+  const int d = x ? e : e - im.new_w;
+  int t[4];
+  resize_table_entry(d, resize_axis_scale(x ? im.new_w : im.new_h, x ? im.W : c.H[f]), x ? im.W : c.H[f], t);
+  *reinterpret_cast<int4*>(tabs + (x ? im.xtab : im.ytab) + 4 * d) = make_int4(t[0], t[1], t[2], t[3]);
 }
 
 // The ragged crop form (fr_resize_images / fr_embed_images): image f of its own size resized to the
@@ -402,6 +440,35 @@ hipError_t launch_letterbox_images(const LetterboxImage* imgs, const int* tabs, 
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(letterbox_images_kernel, dim3((unsigned)((elems / 4 + 255) / 256), n), dim3(256), 0, s, imgs,
                      tabs, dw, dh, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_letterbox_images_by_value(const LetterboxChunk& c, const int* tabs, int n, int dw, int dh,
+                                            uint8_t* out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const long long elems = (long long)dh * dw * 3;
+  if ((dw * 3) % 4 || elems >= (1ll << 31) || n > LETTERBOX_BY_VALUE || (reinterpret_cast<uintptr_t>(out) & 3))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(letterbox_images_args_kernel, dim3((unsigned)((elems / 4 + 255) / 256), n), dim3(256), 0, s, c,
+                     tabs, dw, dh, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_resize_tables(const LetterboxChunk& c, int n, int* tabs, long long tabs_ints, float* scales,
+                                int* raw, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > LETTERBOX_BY_VALUE || !tabs || (reinterpret_cast<uintptr_t>(tabs) & 15)) return hipErrorInvalidValue;
+  int entries = 0;
+  for (int f = 0; f < n; ++f) {
+    const LetterboxImage& im = c.im[f];
+    // every store lies inside the arena, at a 16-byte boundary
+    if (im.new_w < 1 || im.new_h < 1 || im.W < 1 || c.H[f] < 1 || im.xtab < 0 || im.ytab < 0 || (im.xtab & 3) ||
+        (im.ytab & 3) || im.xtab + 4ll * im.new_w > tabs_ints || im.ytab + 4ll * im.new_h > tabs_ints)
+      return hipErrorInvalidValue;
+    entries = entries > im.new_w + im.new_h ? entries : im.new_w + im.new_h;
+  }
+  hipLaunchKernelGGL(resize_tables_kernel, dim3((unsigned)((entries + 255) / 256), n), dim3(256), 0, s, c, tabs,
+                     scales, raw);
   return hipGetLastError();
 }
 

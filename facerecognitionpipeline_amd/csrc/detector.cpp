@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "runtime.h"
+#include "resize_table.h"
 
 using namespace frhip;
 
@@ -64,6 +65,11 @@ struct Detector {
   float* dets = nullptr;
   int* dets_count = nullptr;
   int* tabs = nullptr;  // [det_w + det_h][4]
+  // fr_detect_images_device: the table arena ([max_frames][det_w + det_h][4], image f of a chunk at
+  // f * (det_w + det_h) * 4: an x table has at most det_w entries, a y table det_h) and the
+  // chunk's det_scales [max_frames], both written by resize_tables_kernel
+  int* img_tabs = nullptr;
+  float* img_scales = nullptr;
   int dets_cap = 0;
   bool row_reduce = true;  // row_plan (frt_set_detector_row_reduction switches it off for A/B)
   std::vector<int> htabs;
@@ -360,6 +366,8 @@ int detector_finalize(fr_handle* h) {
   take((void**)&d->dets, B * d->dets_cap * 15 * f4);
   take((void**)&d->dets_count, B * sizeof(int));
   take((void**)&d->tabs, (size_t)(d->det_w + d->det_h) * 4 * sizeof(int));
+  take((void**)&d->img_tabs, B * (size_t)(d->det_w + d->det_h) * 4 * sizeof(int));
+  take((void**)&d->img_scales, B * sizeof(float));
   if (d->ws) FR_HIP(h, hipFree(d->ws));
   d->ws = nullptr;
   FR_HIP(h, hipMalloc(&d->ws, off));
@@ -373,28 +381,11 @@ int detector_finalize(fr_handle* h) {
 
 // cv::resize INTER_LINEAR coefficient table for one axis: (src0, src1, w0, w1) per output
 // (also the resize branch of FaceEmbedder.preprocess, embed_forward.cpp resize_device).
-#pragma clang fp contract(off)
+// The arithmetic of an entry is resize_table.h's, which resize_tables_kernel shares.
 void resize_axis_table(int dsize, int ssize, int* t) {
-  const double scale = 1.0 / ((double)dsize / ssize);
-  for (int d = 0; d < dsize; ++d) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = (int)std::floor(f);
-    f -= (float)s;
-    if (s < 0) {
-      f = 0.f;
-      s = 0;
-    }
-    if (s >= ssize - 1) {
-      f = 0.f;
-      s = ssize - 1;
-    }
-    t[4 * d] = s;
-    t[4 * d + 1] = std::min(s + 1, ssize - 1);
-    t[4 * d + 2] = (int)std::lrint((1.f - f) * 2048.f);
-    t[4 * d + 3] = (int)std::lrint(f * 2048.f);
-  }
+  const double scale = resize_axis_scale(dsize, ssize);
+  for (int d = 0; d < dsize; ++d) resize_table_entry(d, scale, ssize, t + 4 * d);
 }
-#pragma clang fp contract(on)
 
 int resize_simd_end(int row) {
   // SSE2 vertical pass: 16-element chunks while x <= row-16, then 8-element chunks while x < row-8
@@ -595,6 +586,38 @@ int letterbox_images(fr_handle* h, const uint8_t* const* images, const int32_t* 
   return FR_OK;
 }
 
+// The same chunk for fr_detect_images_device: geometry by value in the kernel arguments, tables
+// and scales made on the device in the detector's arena.  Stages nothing, copies nothing, waits
+// for nothing; images and sizes are not read after it returns.
+int letterbox_images_device(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int B, Geometry& g,
+                            hipStream_t s) {
+  Detector* d = h->det;
+  const int DW = d->det_w, DH = d->det_h;
+  if (B > LETTERBOX_BY_VALUE) return fail(h, FR_ERR_INVALID_ARGUMENT, "chunk exceeds the by-value descriptor limit");
+  const int per = (DW + DH) * 4;  // ints of the arena per image
+  LetterboxChunk c{};
+  int max_h = 0;
+  for (int i = 0; i < B; ++i) {
+    Geometry gi;
+    letterbox_size(sizes[2 * i], sizes[2 * i + 1], DW, DH, gi);
+    c.im[i] = LetterboxImage{images[i], sizes[2 * i + 1], gi.new_w, gi.new_h, gi.simd_end, i * per,
+                             i * per + 4 * gi.new_w};
+    c.H[i] = sizes[2 * i];
+    c.scale[i] = (float)gi.det_scale;
+    max_h = std::max(max_h, gi.new_h);
+  }
+  g = Geometry{};
+  g.new_h = max_h;
+  if (d->row_reduce) row_plan(max_h, DH, g);
+  // d->count too: the table kernel zeroes the chunk's candidate counters (postprocess_device: counts_zeroed)
+  hipError_t e =
+      launch_resize_tables(c, B, d->img_tabs, (long long)d->max_frames * per, d->img_scales, d->count, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("resize tables: ") + hipGetErrorString(e));
+  e = launch_letterbox_images_by_value(c, d->img_tabs, B, DW, DH - g.skip1, d->canvas, s);
+  if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("letterbox: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
 int forward_network(fr_handle* h, int B, const Geometry& g, hipStream_t s);
 
 // Letterbox + network for B <= max_frames frames; head maps land in d->hd[0..2].  tabs: the frame
@@ -720,13 +743,14 @@ namespace {
 // The device part of the post-processing: decode + NMS of the B head maps in d->hd into out (device
 // [B][max_out][15], rows i < min(out_count[b], max_out) written) and out_count (device [B], the full
 // kept count); d->count keeps the frames' anchors above det_thresh.  Decode divides by scales[b]
-// (device, per frame) or, when scales is NULL, by det_scale.  Asynchronous.
+// (device, per frame) or, when scales is NULL, by det_scale.  counts_zeroed: an earlier launch of the
+// chunk has zeroed d->count[0..B) (resize_tables_kernel).  Asynchronous.
 int postprocess_device(fr_handle* h, int B, float det_scale, const float* scales, float det_thresh, int max_out,
-                       float* out, int* out_count, hipStream_t s) {
+                       float* out, int* out_count, hipStream_t s, bool counts_zeroed = false) {
   Detector* d = h->det;
   const int DW = d->det_w, DH = d->det_h;
   const int lh[3] = {DH / 8, DH / 16, DH / 32}, lw[3] = {DW / 8, DW / 16, DW / 32};
-  FR_HIP(h, hipMemsetAsync(d->count, 0, B * sizeof(int), s));
+  if (!counts_zeroed) FR_HIP(h, hipMemsetAsync(d->count, 0, B * sizeof(int), s));
   DetDecodeParams dp{};
   int base = 0;
   for (int i = 0; i < 3; ++i) {
@@ -901,6 +925,28 @@ int detector_run_images(fr_handle* h, const uint8_t* const* images, const int32_
     if (rc) return rc;
     rc = postprocess_chunk(h, B, off, 0.f, scales, "image", det_thresh, max_faces, dets, counts, s);
     if (rc) return rc;
+  }
+  return FR_OK;
+}
+
+int detector_run_images_device(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n,
+                               float det_thresh, int max_faces, float* dets, int32_t* counts, hipStream_t s) {
+  Detector* d = h->det;
+  int rc = detector_check_images(h, images, sizes, n);  // all of them, before the first chunk runs
+  if (rc) return rc;
+  for (int off = 0; off < n; off += d->max_frames) {
+    const int B = std::min(d->max_frames, n - off);
+    Geometry g;
+    rc = letterbox_images_device(h, images + off, sizes + 2 * (size_t)off, B, g, s);
+    if (rc) return rc;
+    rc = forward_network(h, B, g, s);
+    if (rc) return rc;
+    // as detector_run_device: NMS writes the caller's rows and counts, then -1 for an image over the limit
+    rc = postprocess_device(h, B, 0.f, d->img_scales, det_thresh, max_faces, dets + (size_t)off * max_faces * 15,
+                            counts + off, s, true);
+    if (rc) return rc;
+    const hipError_t e = launch_det_overflow(d->count, B, DET_MAX_CANDIDATES, counts + off, s);
+    if (e != hipSuccess) return fail(h, FR_ERR_HIP, std::string("detect counts: ") + hipGetErrorString(e));
   }
   return FR_OK;
 }

@@ -265,6 +265,21 @@ struct FitSlots {
 // fit fails gets ok = 0, a NaN map and a descriptor of an empty (0 x 0) source: the warp writes
 // zeros and reads nothing.  n_frames * max_faces < 2^31.
 hipError_t launch_fit_similarity(const FitSlots& p, hipStream_t s);
+// The ragged form (fr_align_images_device): frame f is an image of its own size at its own address.
+// The descriptors travel by value, at most FIT_IMAGES_BY_VALUE per launch: with FitSlots that is
+// 3.3 KB of the 4 KB argument limit (a launch's hidden arguments take a few hundred bytes more); a
+// longer list takes several launches (frhip_runtime.cpp).  The one-size launch keeps FitSlots alone.
+struct FitImage {
+  const uint8_t* src;  // device uint8 [H][W][3]
+  int H, W;
+};
+constexpr int FIT_IMAGES_BY_VALUE = 192;
+struct FitImageSlots {
+  FitSlots s;  // frames, H and W are not read; n_frames = the images of this launch (<= FIT_IMAGES_BY_VALUE)
+  FitImage images[FIT_IMAGES_BY_VALUE];  // frame f is images[f] (entries >= s.n_frames are not read)
+};
+static_assert(sizeof(FitImage) == 16 && sizeof(FitImageSlots) <= 3328, "FitImageSlots fits the kernel arguments");
+hipError_t launch_fit_similarity_images(const FitImageSlots& p, hipStream_t s);
 
 // Laplacian variance (numpy's summation order) of the gray image of n uint8 images [n][H][W][C]
 // (C = 3 / 4: RGB(A) -> gray; C = 1: gray) -> var[n] (double).  Images whose gray copy and
@@ -437,6 +452,26 @@ struct LetterboxImage {
 };
 hipError_t launch_letterbox_images(const LetterboxImage* imgs, const int* tabs, int n, int dw, int dh, uint8_t* out,
                                    hipStream_t s);
+// The same with the descriptors by value in the kernel arguments: a chunk of at most
+// LETTERBOX_BY_VALUE images (the detector's largest max_frames; 2.5 KB of the 4 KB argument limit),
+// each with its source height and its det_scale.  Nothing is staged, so nothing has to be waited for.
+constexpr int LETTERBOX_BY_VALUE = 64;
+struct LetterboxChunk {
+  LetterboxImage im[LETTERBOX_BY_VALUE];
+  int H[LETTERBOX_BY_VALUE];        // source heights (the y tables' ssize)
+  float scale[LETTERBOX_BY_VALUE];  // det_scale = new_h / H as float
+};
+static_assert(sizeof(LetterboxImage) == 32 && sizeof(LetterboxChunk) <= 3072, "a chunk fits the kernel arguments");
+hipError_t launch_letterbox_images_by_value(const LetterboxChunk& c, const int* tabs, int n, int dw, int dh,
+                                            uint8_t* out, hipStream_t s);
+// The chunk's resize tables made on the device (resize_table.h's arithmetic: bitwise
+// resize_axis_table's): image f's x table ([new_w][4], ssize W) at tabs + xtab, its y table
+// ([new_h][4], ssize H[f]) at tabs + ytab, scale[f] into scales[f] and 0 into raw[f] (decode_kernel's
+// count of the image; scales and raw may be NULL).  tabs:
+// device, 16-byte aligned, tabs_ints ints; an offset that is negative, not a multiple of 4 or whose
+// table ends beyond tabs_ints is refused before anything is launched.
+hipError_t launch_resize_tables(const LetterboxChunk& c, int n, int* tabs, long long tabs_ints, float* scales,
+                                int* raw, hipStream_t s);
 // cv2.resize INTER_LINEAR of n images of different sizes (n <= 65535) to 112 x 112 x 3 each (out:
 // [n][112][112][3], 4-byte aligned): image f's tables at tabs + xtab / ytab ([112][4] each).
 struct CropImage {

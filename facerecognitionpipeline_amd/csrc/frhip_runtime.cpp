@@ -548,6 +548,65 @@ int fr_align_device(fr_handle* h, const uint8_t* frames, int n_frames, int heigh
   return FR_OK;
 }
 
+int fr_detect_images_device(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float det_thresh,
+                            int max_faces, float* dets, int32_t* counts, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->detector) return fail(h, FR_ERR_STATE, "not a detector handle (fr_create(\"scrfd_10g\", \"scrfd\", ...))");
+  if (!h->finalized) return fail(h, FR_ERR_STATE, "model not finalised (fr_finalize)");
+  if (max_faces < 1) return fail(h, FR_ERR_INVALID_ARGUMENT, "max_faces must be at least 1");
+  if (n < 0 || (n > 0 && (!images || !sizes || !dets || !counts)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad n or NULL images / sizes / output buffers");
+  if (n == 0) return FR_OK;
+  if (int rc = check_dev_err(h)) return rc;  // reported by earlier asynchronous work
+  DeviceGuard dg(h->device);
+  return detector_run_images_device(h, images, sizes, n, det_thresh, max_faces, dets, counts, (hipStream_t)stream);
+}
+
+int fr_align_images_device(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n_images,
+                           const float* landmarks, int stride, const int32_t* counts, int max_faces, int out_size,
+                           uint8_t* out, double* tforms, uint8_t* ok, void* stream) {
+  if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  const long long slots = (long long)n_images * max_faces;
+  if (n_images < 0 || max_faces < 0 || out_size <= 0 || out_size > 1024 || stride < 10 || slots >= (1ll << 31) ||
+      (slots > 0 && (!images || !sizes || !landmarks || !out || !ok)))
+    return fail(h, FR_ERR_INVALID_ARGUMENT, "bad alignment arguments");
+  if (slots == 0) return FR_OK;
+  for (int i = 0; i < n_images; ++i)
+    if (!images[i] || sizes[2 * i] <= 0 || sizes[2 * i + 1] <= 0)
+      return fail(h, FR_ERR_INVALID_ARGUMENT, "image " + std::to_string(i) + " is NULL or has a side < 1");
+  DeviceGuard dg(h->device);
+  // sized before the first launch; a call that fits the buffer allocates nothing
+  if (int rc = ensure_buf(h, &h->align_slots, &h->align_slots_cap, (size_t)slots * sizeof(WarpFace))) return rc;
+  FitImageSlots q{};
+  FitSlots& p = q.s;
+  p.stride = stride;
+  p.max_faces = max_faces;
+  reference_template(out_size, p.tmpl);
+  fit_logs(&p.logs);
+  hipStream_t s = (hipStream_t)stream;
+  // the image descriptors by value, FIT_IMAGES_BY_VALUE per fit launch: launch c fits the slots of
+  // images [base, base + m) into their places of the one descriptor list the warp reads
+  for (int base = 0; base < n_images; base += FIT_IMAGES_BY_VALUE) {
+    const int m = std::min(FIT_IMAGES_BY_VALUE, n_images - base);
+    const size_t slot0 = (size_t)base * max_faces;
+    p.n_frames = m;
+    for (int i = 0; i < m; ++i)
+      q.images[i] = FitImage{images[base + i], sizes[2 * (base + i)], sizes[2 * (base + i) + 1]};
+    p.landmarks = landmarks + slot0 * stride;
+    p.counts = counts ? counts + base : nullptr;
+    p.tforms = tforms ? tforms + slot0 * 6 : nullptr;
+    p.ok = ok + slot0;
+    p.faces = static_cast<WarpFace*>(h->align_slots) + slot0;
+    const hipError_t e = launch_fit_similarity_images(q, s);
+    if (e != hipSuccess) return launch_fail(h, "similarity fit", e);
+  }
+  const hipError_t e = launch_warp_affine_images(static_cast<WarpFace*>(h->align_slots), (int)slots, out_size, out, s);
+  if (e != hipSuccess) return launch_fail(h, "warp", e);
+  return FR_OK;
+}
+
 int fr_blur_scores_device(fr_handle* h, const uint8_t* crops, int n, int height, int width, int channels,
                           double* scores, void* stream) {
   if (!h) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "NULL handle");

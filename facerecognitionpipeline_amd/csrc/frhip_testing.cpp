@@ -552,6 +552,37 @@ int frt_letterbox_images(const uint8_t* const* images, const int32_t* sizes, con
 
 int frt_resize_simd_end(int row_elems) { return resize_simd_end(row_elems); }
 
+int frt_fit_images_by_value(void) { return FIT_IMAGES_BY_VALUE; }
+
+int frt_resize_axis_table(int dsize, int ssize, int32_t* out) {
+  if (dsize < 1 || ssize < 1 || !out) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_resize_axis_table: bad arguments");
+  resize_axis_table(dsize, ssize, out);
+  return FR_OK;
+}
+
+int frt_resize_tables_device(int dsize, int ssize, int32_t* out) {
+  if (dsize < 1 || ssize < 1 || dsize > (1 << 20) || !out)
+    return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_resize_tables_device: bad arguments");
+  // one image whose x and y axes are both the axis asked for: the kernel's two branches
+  LetterboxChunk c{};
+  c.im[0] = LetterboxImage{nullptr, ssize, dsize, dsize, 0, 0, 4 * dsize};
+  c.H[0] = ssize;
+  const size_t ints = (size_t)dsize * 8;
+  std::vector<int> host(ints);
+  int* tabs = nullptr;
+  hipError_t e = hipMalloc((void**)&tabs, ints * sizeof(int));
+  if (e == hipSuccess) e = launch_resize_tables(c, 1, tabs, (long long)ints, nullptr, nullptr, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), tabs, ints * sizeof(int), hipMemcpyDeviceToHost);
+  (void)hipFree(tabs);
+  if (e == hipErrorInvalidValue) return fail(nullptr, FR_ERR_INVALID_ARGUMENT, "frt_resize_tables_device: refused");
+  if (e != hipSuccess)
+    return fail(nullptr, FR_ERR_HIP, std::string("frt_resize_tables_device: ") + hipGetErrorString(e));
+  if (memcmp(host.data(), host.data() + 4 * (size_t)dsize, 4 * (size_t)dsize * sizeof(int)))
+    return fail(nullptr, FR_ERR_STATE, "frt_resize_tables_device: the x and y tables of one axis differ");
+  memcpy(out, host.data(), 4 * (size_t)dsize * sizeof(int));
+  return FR_OK;
+}
+
 int frt_quality_gate_host(const float* dets, const int32_t* counts, const uint8_t* ok, const double* blur,
                           int n_frames, int max_faces, const fr_gate_config* cfg, uint8_t* stage, double* metrics,
                           int32_t* bbox, int32_t* rank, int32_t* rows, int32_t* frame_offsets, int32_t* valid_slots,

@@ -521,6 +521,10 @@ int detector_forward(fr_handle* h, const uint8_t* frames, int n, int height, int
 // detector_forward_images runs one chunk as detector_run_images runs it.
 int detector_run_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float det_thresh,
                         int max_faces, float* dets, int32_t* counts, hipStream_t s);
+// fr_detect_images_device: detector_run_images' chunks with dets and counts on the device, as
+// detector_run_device writes them; tables and scales made on the device, nothing staged.  Asynchronous.
+int detector_run_images_device(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n,
+                               float det_thresh, int max_faces, float* dets, int32_t* counts, hipStream_t s);
 int detector_forward_images(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n, float* heads,
                             uint8_t* canvas, hipStream_t s);
 // The post-processing alone (frhip_testing.h: frt_detector_postprocess): heads (device, n <= max_frames

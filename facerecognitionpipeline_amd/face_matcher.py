@@ -188,12 +188,14 @@ class FaceMatcher:
         return self.processor
 
     def match_single_image(self, image_path: str, top_k: int = 5, save_visualization: bool = True,
-                           processor=None, exclusive: bool = False) -> Dict:
+                           processor=None, exclusive: bool = False, device_chain: bool = False) -> Dict:
         """face_matcher.py:148-271: every face of the photograph at ``image_path`` (``return_all``: the
         quality gate is reported, not applied) against the gallery -> the reference's dict.
         ``processor`` replaces the ``FaceProcessor`` of the reference's configuration (built on first
-        use otherwise) and is kept for later calls.  ``exclusive``: see :meth:`match_images`, of which
-        this is the one-path case."""
+        use otherwise) and is kept for later calls.  ``exclusive`` and ``device_chain``: see
+        :meth:`match_images`, of which this is the one-path case."""
+        if not isinstance(device_chain, bool):
+            raise ValueError("device_chain must be True or False")
         if processor is not None:
             self.processor = processor
         if not os.path.exists(image_path):
@@ -202,10 +204,10 @@ class FaceMatcher:
             self._print(f"{'=' * 60}")
             raise ValueError(f"Image not found: {image_path}")
         return self.match_images([image_path], top_k=top_k, exclusive=exclusive,
-                                 save_visualization=save_visualization)[0]
+                                 save_visualization=save_visualization, device_chain=device_chain)[0]
 
     def match_images(self, images, top_k: int = 5, exclusive: bool = False, save_visualization: bool = False,
-                     errors: str = "raise") -> List:
+                     errors: str = "raise", device_chain: bool = False) -> List:
         """``match_single_image`` for a sequence of photographs of different sizes -- paths or arrays,
         as ``FaceProcessor.process_images`` takes them (and its ``errors``) -- in one pass: one detect
         call, one align launch at the processor's size and one blur call over all photographs; the
@@ -221,17 +223,38 @@ class FaceMatcher:
         ``fr_photo_rollcall``'s FR_ROLLCALL_EXCLUSIVE): a recognised face also carries ``match_rank``,
         the 1-based rank among its ``top_matches`` that it was given, and a face that lost its top-1 and
         every other match above the threshold has ``recognized: False``, its top-1 as
-        ``best_candidate`` and ``reason: 'claimed_by_other_face'``."""
+        ``best_candidate`` and ``reason: 'claimed_by_other_face'``.
+
+        ``device_chain=True`` runs the photographs through ``device_chain_images`` (the processor must
+        hold the GPU ``FaceDetector``: TypeError otherwise): detections stay in HBM through the fit, the
+        warp, the blur score and the quality gate, the gate's ``rows`` gather the crops into result
+        order on the device and its ``frame_offsets`` are the roll call's offsets, so the only copies
+        to the host are one packed copy of the per-slot outputs per block of the detector's
+        ``max_frames`` photographs and the top-k results.  The same dicts as with ``False`` (metrics as
+        ``FaceProcessor.process_frames`` states); a detection whose similarity fit fails is listed with
+        ``is_valid: False`` where the host path raises."""
+        if not isinstance(device_chain, bool):
+            raise ValueError("device_chain must be True or False")
         processor = self._photo_processor()
-        out, items, faces, crops, blur = processor._detect_align_images(images, errors)
-        per_image, order, at = [], [], 0
-        for (_slot, _image), fs in zip(items, faces):
-            # the gate, sort and dicts of process_numpy, with a crop's position in place of the crop
-            res = processor._gate(fs, np.arange(at, at + len(fs)), None if blur is None else blur[at:at + len(fs)],
-                                  True) if fs else []
-            per_image.append(res)
-            order.extend(int(r["aligned_face"]) for r in res)
-            at += len(fs)
+        if device_chain:
+            if not hasattr(getattr(processor.detector, "model", None), "detect_images_device"):
+                raise TypeError("device_chain=True runs the GPU FaceDetector (detect_images_device); the "
+                                "processor's detector has none")
+            out, items = processor._usable_items(images, errors)
+            # the live crops in result order, image after image: already the embedder's order
+            per_image, crops = processor._chain_images([image for _slot, image in items], True) if items else (
+                [], None)
+            order = list(range(sum(len(r) for r in per_image)))
+        else:
+            out, items, faces, crops, blur = processor._detect_align_images(images, errors)
+            per_image, order, at = [], [], 0
+            for (_slot, _image), fs in zip(items, faces):
+                # the gate, sort and dicts of process_numpy, with a crop's position in place of the crop
+                res = processor._gate(fs, np.arange(at, at + len(fs)),
+                                      None if blur is None else blur[at:at + len(fs)], True) if fs else []
+                per_image.append(res)
+                order.extend(int(r["aligned_face"]) for r in res)
+                at += len(fs)
         n = len(order)
         offsets = np.concatenate([[0], np.cumsum([len(r) for r in per_image])]).astype(np.int64)
         thr = float(self.similarity_threshold)

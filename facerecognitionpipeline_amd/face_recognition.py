@@ -17,7 +17,8 @@ any detector object with the reference's
 Images of different sizes (a folder of photographs) go through ``detect_images`` /
 ``align_images`` / ``FaceProcessor.process_images``: one detect call, one align launch and
 one blur call for the whole sequence (``fr_detect_images`` / ``fr_align_images``), per image
-the single-image arithmetic.
+the single-image arithmetic.  ``process_images(gate="device")`` keeps that pass in HBM
+(``device_chain_images``: ``fr_detect_images_device`` / ``fr_align_images_device``).
 
 Parity of the OpenCV arithmetic is UNPINNED (cv2 absent); the kernels are
 pinned bit-exactly to the restatement in ``oracle/align_ref.py``.
@@ -374,6 +375,82 @@ def device_chain(detector, aligner, quality_filter, frames: torch.Tensor, max_fa
     return host, gate, crops
 
 
+def device_chain_images(detector, aligner, quality_filter, images, max_faces: Optional[int] = None,
+                        with_dets: bool = True, pick=None):
+    """``device_chain`` for a sequence of images of different sizes (host arrays or device tensors,
+    RGB [H,W,3] or gray [H,W]): detect_images_device -> align_images_device -> blur_scores_device ->
+    gate_device back to back, nothing staged and nothing waited for in between, in blocks of the
+    detector's ``max_frames`` images with ONE packed copy of the per-slot outputs per block.  Returns
+    what ``device_chain`` returns, ``(host, gate, crops)``, for the whole sequence: slot numbers
+    (``rows`` / ``valid_slots``) count i * F + k over all images and ``frame_offsets`` runs over all of
+    them, so ``chain_faces(quality_filter, host, i)`` lists image i.
+
+    The crops of a block's slots take len(block) * F * S * S * 3 bytes.  With ``pick`` that is all
+    the chain holds: ``pick(host, gate, crops)`` is called per block with the block's own outputs
+    (slot numbers local to the block) and returns the crops to keep, a uint8 [m,S,S,3] device tensor
+    (``crops[gate["rows"][:total].long()]``, say); the returned ``crops`` are the kept ones, block after
+    block.  Without it the crops of every slot of every image are returned, [n*F,S,S,3].
+
+    Needs the GPU ``FaceDetector``: a detector without ``detect_images_device`` raises TypeError.  An
+    image over the detector's 4096-candidate limit raises the ``NotImplementedError``
+    ``FaceDetector.detect_images`` raises."""
+    model = getattr(detector, "model", None)
+    if not hasattr(model, "detect_images_device"):
+        raise TypeError("the device chain for images runs the GPU FaceDetector (detect_images_device); "
+                        "this detector has none")
+    dev = aligner._ops.device
+    frames = [_device_frame(im, dev) for im in images]
+    n = len(frames)
+    F = detector.max_faces if max_faces is None else int(max_faces)
+    S = aligner.output_size
+    B = max(1, int(model.max_batch))
+    hosts, gates, kept = [], [], []
+    for first in range(0, max(n, 1), B):
+        block = frames[first:first + B]
+        dets, counts = model.detect_images_device(block, detector.det_thresh, F)
+        crops, _, ok = aligner._ops.handle.align_images_device(block, dets, counts, S)
+        crops = crops.view(len(block) * F, S, S, 3)
+        blur = quality_filter._ops.handle.blur_scores_device(crops) if quality_filter.check_blur else None
+        gate = quality_filter.gate_device(dets, counts, ok, blur)
+        host = tensors_to_host({**gate, "counts": counts, **({"dets": dets} if with_dets else {})})
+        for f in np.flatnonzero(host["counts"] < 0):
+            raise NotImplementedError(f"image {first + f} has more than 4096 anchors above det_thresh (limit 4096)")
+        hosts.append(host)
+        gates.append(gate)
+        kept.append(crops if pick is None else pick(host, gate, crops))
+    if len(hosts) == 1:
+        return hosts[0], gates[0], kept[0]
+    return _merge_chain_blocks(hosts, F), _merge_chain_blocks(gates, F, hosts), torch.cat(kept)
+
+
+def _merge_chain_blocks(blocks: List[Dict], F: int, hosts: Optional[List[Dict]] = None) -> Dict:
+    """The gate outputs of consecutive blocks of images as those of one call over all of them: per-slot
+    arrays back to back, the packed lists with each block's slot numbers moved behind the blocks before
+    it.  ``blocks`` are host arrays, or (``hosts``: the same blocks on the host, for the totals)
+    device tensors."""
+    on_host = hosts is None
+    hosts = blocks if on_host else hosts
+    cat = np.concatenate if on_host else torch.cat
+    out = {k: cat([b[k] for b in blocks]) for k in blocks[0] if k not in ("rows", "valid_slots", "frame_offsets",
+                                                                           "n_valid")}
+    rows, valid, offsets, first, faces = [], [], [blocks[0]["frame_offsets"][:1]], 0, 0
+    for b, h in zip(blocks, hosts):
+        nb = h["stage"].shape[0]
+        rows.append(b["rows"][:int(h["frame_offsets"][nb])] + first * F)
+        valid.append(b["valid_slots"][:int(h["n_valid"][0])] + first * F)
+        offsets.append(b["frame_offsets"][1:] + faces)
+        first += nb
+        faces += int(h["frame_offsets"][nb])
+    fill = (lambda m: np.full(m, -1, np.int32)) if on_host else (
+        lambda m: torch.full((m,), -1, dtype=torch.int32, device=blocks[0]["rows"].device))
+    n_valid = sum(int(h["n_valid"][0]) for h in hosts)
+    out["rows"] = cat(rows + [fill(first * F - faces)])
+    out["valid_slots"] = cat(valid + [fill(first * F - n_valid)])
+    out["frame_offsets"] = cat(offsets)
+    out["n_valid"] = blocks[0]["n_valid"] * 0 + n_valid
+    return out
+
+
 def chain_faces(quality_filter, host: Dict[str, np.ndarray], f: int) -> List[Dict]:
     """Frame ``f`` of ``device_chain``'s host outputs as ``process_numpy(frame, return_all=True)``
     lists it (descending det_score x blur_score, equal keys in detection order), each dict with
@@ -484,7 +561,7 @@ class FaceProcessor:
             raise ValueError(f"Could not load image: {image_path}")
         return self.process_numpy(image_rgb, return_all)
 
-    def process_images(self, images, return_all: bool = False, errors: str = "raise") -> List:
+    def process_images(self, images, return_all: bool = False, errors: str = "raise", gate: str = "host") -> List:
         """``process_numpy`` / ``process_image`` for a sequence of images of different sizes -- arrays
         (RGB [H,W,3] or gray [H,W]) or paths, mixed freely -- with the GPU work batched across the
         sequence: one ``detect_images`` call (chunked by the detector's ``max_frames``), one
@@ -505,7 +582,21 @@ class FaceProcessor:
         maps differ by fp32 rounding: the same faces, det_score within 1e-5 and boxes within 1 px where
         scores are distinct.  On smooth content (a wall, a sky, a tiny image upscaled) neighbouring
         anchors score equal to the last bits, and NMS may then keep a neighbouring box of the same
-        score in one path and not the other ("Mixed-size image batches")."""
+        score in one path and not the other ("Mixed-size image batches").
+
+        ``gate="device"`` keeps the whole pass on the device (``device_chain_images``): detections are
+        fitted, warped, scored and gated where they are, one packed copy per block of the detector's
+        ``max_frames`` images brings the per-slot outputs over, and only the crops that are returned --
+        every live one (``return_all``) or the first valid one of each image -- are gathered on the
+        device (through the gate's ``rows`` / ``valid_slots``) and copied.  Against ``gate="host"``:
+        the same faces in the same order, the same ``is_valid``, boxes, landmarks and crop bytes;
+        metrics as ``process_frames`` states.  A detection whose similarity fit fails comes back
+        ``is_valid: False`` with an all-zero crop, where the host path raises.  Needs the GPU
+        ``FaceDetector`` (TypeError otherwise)."""
+        if gate not in ("host", "device"):
+            raise ValueError('gate must be "host" or "device"')
+        if gate == "device":
+            return self._process_images_device(images, return_all, errors)
         out, items, faces, crops, blur = self._detect_align_images(images, errors)
         at = 0
         for (slot, image), fs in zip(items, faces):
@@ -524,6 +615,23 @@ class FaceProcessor:
         usable ones as (slot, image as process_numpy would get it); ``faces[j]`` the detector's faces of
         ``items[j]``; ``crops`` uint8 [total,S,S,3] on the device, image by image in face order; ``blur``
         their float64 blur scores on the host, or None (not checked, or no face)."""
+        out, items = self._usable_items(images, errors)
+        dev = self.aligner._ops.device
+        frames = [_device_frame(image, dev) for _slot, image in items]
+        if hasattr(self.detector, "detect_images"):
+            faces = self.detector.detect_images(frames) if frames else []
+        else:
+            faces = [self.detector.detect(image) for _slot, image in items]
+        crops = self.aligner.align_images(frames, [np.stack([f["landmarks"] for f in fs]) if fs else
+                                                   np.zeros((0, 5, 2), np.float32) for fs in faces])
+        blur = (self.quality_filter.compute_blur_scores(crops)
+                if self.quality_filter.check_blur and crops.shape[0] else None)
+        return out, items, faces, crops, blur
+
+    @staticmethod
+    def _usable_items(images, errors: str):
+        """-> (out, items): ``out`` one slot per item of ``images``, None or the ValueError of an item that
+        cannot be used; ``items`` the usable ones as (slot, image as process_numpy would get it)."""
         if errors not in ("raise", "return"):
             raise ValueError('errors must be "raise" or "return"')
         out: List = [None] * len(images)
@@ -543,17 +651,56 @@ class FaceProcessor:
                 out[slot] = e
                 continue
             items.append((slot, image))
-        dev = self.aligner._ops.device
-        frames = [_device_frame(image, dev) for _slot, image in items]
-        if hasattr(self.detector, "detect_images"):
-            faces = self.detector.detect_images(frames) if frames else []
-        else:
-            faces = [self.detector.detect(image) for _slot, image in items]
-        crops = self.aligner.align_images(frames, [np.stack([f["landmarks"] for f in fs]) if fs else
-                                                   np.zeros((0, 5, 2), np.float32) for fs in faces])
-        blur = (self.quality_filter.compute_blur_scores(crops)
-                if self.quality_filter.check_blur and crops.shape[0] else None)
-        return out, items, faces, crops, blur
+        return out, items
+
+    def _chain_images(self, images, return_all: bool):
+        """``device_chain_images`` over usable images, keeping on the device only the crops a caller
+        hands on -- every live one in result order (``return_all``) or the first valid one of each
+        image -- -> (per_image, crops): ``per_image[j]`` image j's ``chain_faces`` dicts that are kept,
+        ``crops`` uint8 [m,S,S,3] on the device, one per kept face, image after image."""
+        model = getattr(self.detector, "model", None)
+        if not hasattr(model, "detect_images_device"):
+            raise TypeError("the device chain for images runs the GPU FaceDetector (detect_images_device); "
+                            "this detector has none")
+        F = self.detector.max_faces
+
+        def pick(host, gate, crops):
+            if return_all:
+                picked = gate["rows"][:int(host["frame_offsets"][-1])]  # the live slots, image by image
+            else:
+                valid = host["valid_slots"][:int(host["n_valid"][0])]
+                first = np.flatnonzero(np.diff(valid // F, prepend=-1) != 0)  # the first valid slot of each image
+                picked = gate["valid_slots"][torch.from_numpy(first).to(crops.device)]
+            return crops[picked.long()]
+
+        host, _gate, crops = device_chain_images(self.detector, self.aligner, self.quality_filter, images, F,
+                                                 pick=pick)
+        per_image = [chain_faces(self.quality_filter, host, j) for j in range(len(images))]
+        if not return_all:
+            per_image = [[x for x in faces if x["is_valid"]][:1] for faces in per_image]
+        return per_image, crops
+
+    def _process_images_device(self, images, return_all: bool, errors: str) -> List:
+        if not hasattr(getattr(self.detector, "model", None), "detect_images_device"):
+            raise TypeError("gate=\"device\" runs the GPU FaceDetector (detect_images_device); this detector has none")
+        out, items = self._usable_items(images, errors)
+        if not items:
+            return out
+        per_image, crops = self._chain_images([image for _slot, image in items], return_all)
+        aligned = crops.cpu().numpy()
+        at = 0
+        for (slot, image), faces in zip(items, per_image):
+            res = []
+            for x in faces:
+                crop = aligned[at]
+                at += 1
+                if image.ndim == 2:  # a gray image's crops go back 2-D, as in process_numpy
+                    crop = np.ascontiguousarray(crop[..., 0])
+                res.append({"aligned_face": crop, **{k: x[k] for k in ("bbox", "landmarks", "det_score",
+                                                                        "quality_metrics", "is_valid")}})
+            out[slot] = res
+        assert at == len(aligned)
+        return out
 
     def process_numpy(self, image_rgb: np.ndarray, return_all: bool = False) -> List[Dict]:
         faces = self.detector.detect(image_rgb)

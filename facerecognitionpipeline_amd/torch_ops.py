@@ -26,6 +26,8 @@ returns for a ``FaceEmbedder`` / ``_lib.Handle``:
     dets, counts = torch.ops.frhip.detect(frames_u8_nhwc, det_hid, 0.5, 16)            # [N,16,15] f32, [N] i32
     crops, tforms, ok = torch.ops.frhip.align_detections(frames, dets, counts, 112)    # [N,16,112,112,3] u8, f64, u8
     blur = torch.ops.frhip.blur_scores(crops.flatten(0, 1))                            # [N*16] f64
+    dets, counts = torch.ops.frhip.detect_images([img0, img1], det_hid, 0.5, 16)       # images of different sizes
+    crops, tforms, ok = torch.ops.frhip.align_image_detections([img0, img1], dets, counts, 112)
 
 Each op has a fake (meta) implementation, so the ops trace under
 ``torch.fx`` / ``torch.export`` with the right output shapes.
@@ -73,7 +75,7 @@ _utility: Dict[torch.device, "_lib.Handle"] = {}
 
 def utility_handle(device) -> "_lib.Handle":
     """A model-less handle on ``device`` for the entry points that need no weights
-    (``augment_faces``, ``track_consensus``, ``photo_rollcall``, ``capture_tracks``, ``live_tracks``, ``server_tracks``, ``identity_scores``, ``eval_probes``, ``align_detections``, ``blur_scores``): one per device, created on first use."""
+    (``augment_faces``, ``track_consensus``, ``photo_rollcall``, ``capture_tracks``, ``live_tracks``, ``server_tracks``, ``identity_scores``, ``eval_probes``, ``align_detections``, ``align_image_detections``, ``blur_scores``): one per device, created on first use."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"facerecognitionpipeline_amd runs on a HIP device only (no CPU fallback); got {device}")
@@ -335,6 +337,46 @@ def _(frames, dets, counts, out_size):
     n, f = dets.shape[0], dets.shape[1]
     return (frames.new_empty((n, f, out_size, out_size, 3), dtype=torch.uint8),
             frames.new_empty((n, f, 2, 3), dtype=torch.float64), frames.new_empty((n, f), dtype=torch.uint8))
+
+
+# The same two for images of different sizes (fr_detect_images_device / fr_align_images_device):
+# a list of uint8 [H,W,3] tensors, outputs as ``detect`` / ``align_detections`` give them.
+@torch.library.custom_op("frhip::detect_images", mutates_args=())
+def detect_images(images: List[torch.Tensor], handle: int, det_thresh: float,
+                  max_faces: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    for i, im in enumerate(images):
+        if im.device.type != "cuda":
+            raise ValueError(f"image {i} is on {im.device}: detect_images runs on a HIP device (no CPU fallback)")
+    return _get(handle).detect_images_device(images, det_thresh, max_faces)
+
+
+@detect_images.register_fake
+def _(images, handle, det_thresh, max_faces):
+    n = len(images)
+    dev = images[0].device if n else _get(handle).device
+    return (torch.empty((n, max_faces, 15), dtype=torch.float32, device=dev),
+            torch.empty((n,), dtype=torch.int32, device=dev))
+
+
+@torch.library.custom_op("frhip::align_image_detections", mutates_args=())
+def align_image_detections(images: List[torch.Tensor], dets: torch.Tensor, counts: torch.Tensor,
+                           out_size: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    for i, im in enumerate(images):
+        if im.device.type != "cuda":
+            raise ValueError(f"image {i} is on {im.device}: align_image_detections runs on a HIP device "
+                             "(no CPU fallback)")
+    if dets.device.type != "cuda":
+        raise ValueError(f"dets are on {dets.device}: align_image_detections runs on a HIP device (no CPU fallback)")
+    if dets.dim() != 3 or dets.shape[2] != 15:
+        raise ValueError("expected detection rows float32 [N,F,15] (frhip::detect_images' dets)")
+    return utility_handle(dets.device).align_images_device(images, dets, counts, out_size)
+
+
+@align_image_detections.register_fake
+def _(images, dets, counts, out_size):
+    n, f = dets.shape[0], dets.shape[1]
+    return (dets.new_empty((n, f, out_size, out_size, 3), dtype=torch.uint8),
+            dets.new_empty((n, f, 2, 3), dtype=torch.float64), dets.new_empty((n, f), dtype=torch.uint8))
 
 
 @torch.library.custom_op("frhip::blur_scores", mutates_args=())

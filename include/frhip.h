@@ -608,6 +608,45 @@ int fr_align_device(fr_handle* h, const uint8_t* frames /* device [n_frames][hei
                     const int32_t* counts /* device [n_frames] or NULL */, int max_faces, int out_size,
                     uint8_t* out, double* tforms, uint8_t* ok, void* stream);
 
+/* ---- The same chain for images of different sizes (a folder of photographs): fr_detect_images and
+ * fr_align_images with every output in device memory.  Like the three calls above they are
+ * asynchronous on `stream`, synchronise nothing and stage nothing: images and sizes (host arrays,
+ * as fr_detect_images takes them) are read before the call returns and never after, so the caller
+ * may free or overwrite them at once.  The images themselves must stay alive until the stream
+ * reaches the end of the call's work.  A chunk is kernel launches only (its first launch makes the
+ * tables and zeroes the chunk's candidate counters), so after one warm-up call the chain with
+ * fr_blur_scores_device and fr_quality_gate_device captures into a hipGraph and replays to the eager
+ * results (the workspace rule above holds for them too). */
+
+/* fr_detect_images with dets (device float [n][max_faces][15]) and counts (device int32 [n]) on the
+ * device.  The chunk rule, the row-reduction rule and the argument checks are fr_detect_images'
+ * (nothing runs when any image is refused; the message names the image); counts[i] and rows
+ * k < min(counts[i], max_faces) are bitwise fr_detect_images' (the other rows are not written).  An
+ * image with more than 4096 anchors above det_thresh gets counts[i] = -1 (its rows are unspecified);
+ * the other images are unaffected.  Each image's resize tables and det_scale are made on the device
+ * by one kernel per chunk (the host's arithmetic, bitwise) in an arena planned with the detector's
+ * workspace; the per-image geometry travels in the kernel arguments.  Allocates nothing after the
+ * handle's first detect call. */
+int fr_detect_images_device(fr_handle* h, const uint8_t* const* images /* host [n] device pointers */,
+                            const int32_t* sizes /* host [n][2] = height, width */, int n, float det_thresh,
+                            int max_faces, float* dets /* device [n][max_faces][15] */,
+                            int32_t* counts /* device [n] */, void* stream);
+
+/* fr_align_device with a source per image: slot j = i * max_faces + k reads image i (images / sizes as
+ * fr_align_images takes them, any side >= 1).  Liveness, ok, the zero crop and the NaN tform of a slot
+ * that is not live or not fitted are fr_align_device's; for a live, fitted slot out[j] and tforms[j]
+ * are bitwise fr_align_images' for that face.  No pixel of an image with counts[i] <= 0 is read (its
+ * pointer must still be non-NULL).  The image descriptors travel in the fit kernel's arguments, 192
+ * images per launch (a longer list takes several fit launches); the warp is one launch over all slots.
+ * Any handle will do.  Allocates only when the call has more slots than any before it.
+ * FR_ERR_INVALID_ARGUMENT: fr_align_device's, plus (with the image's index in the message) a NULL
+ * image pointer or a side < 1; nothing runs then.  Zero slots is a no-op. */
+int fr_align_images_device(fr_handle* h, const uint8_t* const* images, const int32_t* sizes, int n_images,
+                           const float* landmarks /* device */, int stride,
+                           const int32_t* counts /* device [n_images] or NULL */, int max_faces, int out_size,
+                           uint8_t* out /* device [n_images * max_faces][S][S][3] */,
+                           double* tforms /* device or NULL */, uint8_t* ok /* device */, void* stream);
+
 /* fr_blur_scores with scores in device memory (double [n]): the same launches, no copy and no
  * synchronisation; the values are bitwise fr_blur_scores'. */
 int fr_blur_scores_device(fr_handle* h, const uint8_t* crops, int n, int height, int width, int channels,

@@ -193,6 +193,14 @@ int frt_letterbox_images(const uint8_t* const* images, const int32_t* sizes, con
                          int dh, uint8_t* out, void* stream);
 /* The host's resize_simd_end: where the SSE2-rounded part of a resized row of row_elems bytes ends. */
 int frt_resize_simd_end(int row_elems);
+/* The resize coefficient table of one axis, [dsize][4] = (src0, src1, w0, w1): frt_resize_axis_table
+ * the host's (resize_axis_table), frt_resize_tables_device resize_tables_kernel's for an image whose
+ * two axes are both (dsize, ssize), copied back (its x and y tables must agree: FR_ERR_STATE
+ * otherwise).  out: host int32 [dsize][4].  Synchronises. */
+int frt_resize_axis_table(int dsize, int ssize, int32_t* out);
+int frt_resize_tables_device(int dsize, int ssize, int32_t* out);
+/* FIT_IMAGES_BY_VALUE: the images one fit launch of fr_align_images_device takes by value. */
+int frt_fit_images_by_value(void);
 
 /* fr_quality_gate_device on the CPU: the same per-slot arithmetic (csrc/gate_math.h, compiled for the
  * host) and the same rank / pack rules, every buffer in host memory; no handle, no stream.  The
